@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X LETKF analysis core on BASELINE.json's headline metric.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (headline figure,
+the timed steps' own per-kernel times and roofline).  --full adds every other leg as `detail`:
+the member<->column transposes, the 16-variable cycle, the C4 / C5 / host-memory
+configurations and the CPU baselines (each can be dropped again with its --no-... option).
+--dump-outputs DIR writes what the last timed step left its caller (see dump_outputs).
 
 A "step" is one cwbl_analyze_var call on the configuration's full synthetic grid, i.e. one
 pass of the reference's per-variable hot loop (module_letkf_core.f90:63-64 + 209-240):
@@ -631,6 +637,32 @@ def distinct_devices(world, dev):
     return len({int(v.item()) for v in out})
 
 
+DUMP_SAMPLE = 1 << 23   # elements of var kept by --dump-outputs (32 MB of fp32), all ranks together
+DUMP_SEED = 20240521
+DUMP_STATS = ("points", "solved", "nobs_sum", "lz_truncated", "nonconverged", "q1_undefined",
+              "sweeps_sum", "max_p", "max_sweeps")
+
+
+def dump_outputs(path, var, st, rank, world):
+    """--dump-outputs: what the last timed cwbl_analyze_var call left its caller, as .npy files
+    under `path` (this rank's, named *_rank<r> when there are several ranks):
+      var    float32, the analysed slab var(nx,ny,nz,0:k-1) (updated in place by every warm-up
+             and timed step); whole when it has at most DUMP_SAMPLE / ranks elements, else its
+             elements at a fixed sorted sample of flat indices (numpy default_rng(DUMP_SEED),
+             the same for every run of the same configuration and rank count);
+      stats  float64, the call's cwbl_stats counters in DUMP_STATS order (no timings)."""
+    os.makedirs(path, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    flat = var.reshape(-1)
+    cap = DUMP_SAMPLE // world
+    if flat.numel() > cap:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, flat.numel(), cap))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    np.save(os.path.join(path, f"var{sfx}.npy"), flat.cpu().numpy().astype(np.float32, copy=False))
+    np.save(os.path.join(path, f"stats{sfx}.npy"),
+            np.array([getattr(st, n) for n in DUMP_STATS], np.float64))
+
+
 class Stage:
     """The part of the run in progress, for the error line a failure prints (CWBL_BENCH_FAIL_AT
     = <stage name> raises there: the tests' failure injection)."""
@@ -661,17 +693,26 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="c2")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the detail legs: transposes, cycle, C4 / C5 / host-memory "
+                         "configurations and the CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baselines")
     ap.add_argument("--no-transposes", action="store_true",
-                    help="cycle without the member<->column transposes and write_mean")
+                    help="with --full: cycle without the member<->column transposes and write_mean")
     ap.add_argument("--no-cycle", action="store_true",
-                    help="skip the wall-clock-per-cycle detail (16 var_update entries)")
+                    help="with --full: skip the wall-clock-per-cycle detail (16 var_update "
+                         "entries)")
     ap.add_argument("--no-detail-configs", action="store_true",
-                    help="skip the C4 / C5 / host-memory detail legs")
+                    help="with --full: skip the C4 / C5 / host-memory detail legs")
     ap.add_argument("--big-path", type=int, choices=(0, 1), default=None,
                     help="CWBL_OPT_BIG_PATH for k > 64 (default: the library's, 1 = hand-off; "
                          "0 = one 256-thread kernel)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.big_path is not None:
         CORE_OPTIONS["big_path"] = args.big_path
 
@@ -802,13 +843,19 @@ def run(args, rank, world, stage):
                   flush=True)
             return {"error": repr(e)}
 
-    stage("detail")
-    tr_detail = None if args.no_transposes else guarded(time_transposes, core, w, k, rank,
-                                                        world, dev)
-    cycle = None if args.no_cycle else guarded(time_cycle, core, w, rank, world, dev, x, y, alt,
-                                               transposes=not args.no_transposes)
+    if args.dump_outputs:
+        stage("dump")
+        dump_outputs(args.dump_outputs, var, stats[-1], rank, world)
+
+    stage("detail")  # (every leg of it only with --full)
+    tr_detail = cycle = None
+    if args.full and not args.no_transposes:
+        tr_detail = guarded(time_transposes, core, w, k, rank, world, dev)
+    if args.full and not args.no_cycle:
+        cycle = guarded(time_cycle, core, w, rank, world, dev, x, y, alt,
+                        transposes=not args.no_transposes)
     legs = {}
-    if not args.no_detail_configs and args.config == "c2":
+    if args.full and not args.no_detail_configs and args.config == "c2":
         # the other configurations on the same clock (detail; the library is re-initialised
         # per leg, so the headline core is finished first)
         del slab, var
@@ -888,7 +935,7 @@ def run(args, rank, world, stage):
             },
             "cpu_baseline": None,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # the reference's own compiled path when it travelled with the tree (built in
             # the container that has /root/reference), else the C restatement (port)
             ref = guarded(cpu_baseline_reference, w)

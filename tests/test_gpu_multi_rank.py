@@ -129,7 +129,7 @@ def test_bench_two_ranks_end_to_end():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, CWBL_DIST_BACKEND="gloo")
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "1", "--warmup", "0",
-                        "--no-cpu-baseline", "--no-detail-configs"], cwd=root, env=env,
+                        "--full", "--no-cpu-baseline", "--no-detail-configs"], cwd=root, env=env,
                        capture_output=True, text=True, timeout=850)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

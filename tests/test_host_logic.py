@@ -174,6 +174,42 @@ def test_baseline_process_count_follows_affinity_and_quota():
     assert f"{procs} used" in note
 
 
+def test_dump_outputs_writes_a_fixed_sample_and_the_counters(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: var whole when it fits the budget, else its elements at a
+    seeded sorted sample of flat indices that is the same on every call; the last step's
+    counters (no timings) as float64; per-rank file names when there are several ranks."""
+    import os
+    import sys
+
+    import torch
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    from cwbl import abi
+    var = torch.arange(2 * 3 * 5 * 7, dtype=torch.float32).reshape(2, 3, 5, 7)
+    st = abi.Stats()
+    st.points, st.solved, st.nobs_sum, st.max_p, st.max_sweeps = 210, 200, 4321, 37, 3
+    st.ms_total = 9.5
+    bench.dump_outputs(str(tmp_path / "a"), var, st, 0, 1)
+    assert sorted(os.listdir(tmp_path / "a")) == ["stats.npy", "var.npy"]
+    got = np.load(tmp_path / "a" / "var.npy")
+    assert got.dtype == np.float32
+    np.testing.assert_array_equal(got, var.numpy().ravel())
+    s = np.load(tmp_path / "a" / "stats.npy")
+    assert s.dtype == np.float64 and len(s) == len(bench.DUMP_STATS)
+    assert dict(zip(bench.DUMP_STATS, s)) == dict(
+        points=210, solved=200, nobs_sum=4321, lz_truncated=0, nonconverged=0, q1_undefined=0,
+        sweeps_sum=0, max_p=37, max_sweeps=3)
+    # over the budget: 64 of the 210 elements for each of two ranks, the same ones every time
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 128)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), var, st, 1, 2)
+    assert sorted(os.listdir(tmp_path / "b")) == ["stats_rank1.npy", "var_rank1.npy"]
+    b, c = (np.load(tmp_path / d / "var_rank1.npy") for d in ("b", "c"))
+    assert b.shape == (64,) and b.dtype == np.float32
+    np.testing.assert_array_equal(b, c)
+    assert (np.diff(b) >= 0).all() and b.min() >= 0 and b.max() < 210  # values are the indices
+
+
 def _bench_json(stdout):
     import json
     lines = [l for l in stdout.splitlines() if l.startswith("{")]
