@@ -182,6 +182,8 @@ struct ObsType {
   int family = 0, type_id = 0, nvar = 1, nobs = 0;
   std::vector<float> xyz;   // host copy (3,nobs) for tree builds
   DevBuf obs, error, hdxb, qc;
+  DevBuf dxyz;              // xyz on the device, uploaded by the first device bin build
+  bool dxyz_ok = false;
 };
 
 // One k-d tree of an obs type and its column tables.  The tree depends only on the obs
@@ -196,10 +198,27 @@ struct TreeBufs {
   DevBuf bxyz, bstart;  // uniform bins of the same coordinates (search_binned_kernel)
   HostTree host;
   HostBins bins;
+  // CWBL_OPT_INDEX = 1: the bins come from the device (ncoord: the normalised coordinates in
+  // obs order, which are also the solve's rdata), the tree from a host worker thread that is
+  // joined when a search first needs the tree (tree_ready: built, checked and uploaded)
+  int mode = 0;
+  int n = 0, bin_div_used = 0;
+  DevBuf ncoord;
+  IndexBounds bounds{};
+  std::thread worker;
+  bool worker_started = false, worker_joined = false, tree_ready = false;
+  double worker_ms = 0.0;
+  void join() {
+    if (worker.joinable()) worker.join();
+    worker_joined = worker_started;
+  }
   void release() {
+    join();
     nodes.release(); rdata.release(); ind.release(); col_bg.release();
     col_omm.release(); col_err.release(); col_ok.release(); bxyz.release(); bstart.release();
+    ncoord.release();
   }
+  ~TreeBufs() { join(); }
 };
 
 enum KernelId {
@@ -241,6 +260,11 @@ struct State {
   DevBuf quad;                                        // x^-1/2 quadrature tables
   DevBuf wsa;                                         // hand-off records (split KP=40 path)
   DevBuf flags;                                       // binned search: flagged points (+ count)
+  int index_mode = 0;                                 // CWBL_OPT_INDEX
+  DevBuf tdesc_tree;                                  // index mode 1: the tree searches' table
+  DevBuf ix_keys[2], ix_vals[2], ix_hist, ix_part;    // device bin build scratch
+  PinBuf ix_pin;                                      // its bounds read-back; the flag counts
+  std::vector<hipEvent_t> pevents;                    // cwbl_prep_info timing
   bool binned = true;                                 // CWBL_OPT_SEARCH = 1: k-d tree search only
   int bin_div = 0;  // CWBL_OPT_BIN_DIV: bin side = radius / bin_div (0: by density, bin_div_for)
   bool pageable_register = true;                      // CWBL_OPT_PAGEABLE = 1: bounce slots
@@ -476,6 +500,14 @@ hipError_t order_after_caller() {
 // (more than 24 per r/2 cell on average over the set's bounding box: the finer cells trim
 // the per-row runs closer to the ball).  r4 A/B: C5 (49 per r/2 cell) 15.95 M pts/s at r/2,
 // 16.04 at r/3, 16.19 at r/4; C2 (~11 per cell) 59.4 / 58.9 / 58.6.  CWBL_OPT_BIN_DIV forces it.
+int bin_div_density(int n, const float lo[3], const float hi[3], int dim) {
+  if (n == 0) return 2;
+  const double h = 0.5 * std::sqrt((double)search_r2());
+  double cells = 1.0;
+  for (int c = 0; c < dim; ++c) cells *= std::max(1.0, ((double)hi[c] - (double)lo[c]) / h);
+  return (double)n / cells > 24.0 ? 4 : 2;
+}
+
 int bin_div_for(const HostTree &t, int dim) {
   if (S.bin_div > 0) return S.bin_div;
   const int n = t.n;
@@ -491,16 +523,189 @@ int bin_div_for(const HostTree &t, int dim) {
     }
     seen = true;
   }
-  const double h = 0.5 * std::sqrt((double)search_r2());
-  double cells = 1.0;
-  for (int c = 0; c < dim; ++c) cells *= std::max(1.0, ((double)hi[c] - (double)lo[c]) / h);
-  return (double)n / cells > 24.0 ? 4 : 2;
+  return bin_div_density(n, lo, hi, dim);
+}
+
+// ---- cwbl_prep_info: what the current cwbl_analyze_var spends on its search index -----------
+cwbl_prep_info_t P;
+struct PrepSpan { int ev; int kind; };  // kind 0: bins (device build), 1: columns
+std::vector<PrepSpan> g_pspans;
+int g_pev_used = 0;
+
+double ms_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+hipError_t prep_begin(hipStream_t s, int kind) {
+  while ((int)S.pevents.size() < g_pev_used + 2) {
+    hipEvent_t e;
+    hipError_t r = hipEventCreate(&e);
+    if (r != hipSuccess) return r;
+    S.pevents.push_back(e);
+  }
+  g_pspans.push_back({g_pev_used, kind});
+  g_pev_used += 2;
+  return hipEventRecord(S.pevents[g_pspans.back().ev], s);
+}
+
+hipError_t prep_end(hipStream_t s) { return hipEventRecord(S.pevents[g_pspans.back().ev + 1], s); }
+
+void prep_collect() {  // after a synchronisation of S.stream
+  for (const PrepSpan &p : g_pspans) {
+    float ms = 0.0f;
+    if (hipEventElapsedTime(&ms, S.pevents[p.ev], S.pevents[p.ev + 1]) != hipSuccess) {
+      (void)hipGetLastError();
+      continue;
+    }
+    (p.kind == 0 ? P.ms_bins : P.ms_columns) += ms;
+  }
+  g_pspans.clear();
+  g_pev_used = 0;
+}
+
+// The device bin build (cwbl_index.hip) of n > 0 points on stream s.  have_bounds: `bounds` is
+// that of an earlier build of the same coordinates (ncoord is then current too); otherwise
+// dxyz(3,n) is normalised into ncoord and the bounds are reduced and read back (one
+// synchronisation of s).  div_opt: the divisor, 0 = by density.  Fills the grid of `bins`
+// and, unless grid_only, bxyz / bstart; *skeys / *svals (nullable) point at the sorted cell
+// ids and obs indices in the scratch buffers, valid until the next build.
+int device_bins(hipStream_t s, const float *dxyz, int n, int tdim, float hinv, float vinv,
+                int div_opt, bool have_bounds, IndexBounds &bounds, DevBuf &ncoord,
+                HostBins &bins, int &div_used, bool grid_only, DevBuf *bxyz, DevBuf &bstart,
+                const int **skeys = nullptr, const int **svals = nullptr) {
+  if (!have_bounds) {
+    const int nblk = index_bound_blocks(n);
+    const size_t pbytes = (size_t)nblk * kIndexBoundWords * sizeof(float);
+    HIPCHK(ncoord.ensure((size_t)n * sizeof(float4)));
+    HIPCHK(S.ix_part.ensure(pbytes));
+    HIPCHK(S.ix_pin.ensure(std::max<size_t>(pbytes, 64)));
+    HIPCHK(launch_index_normalize(s, dxyz, n, tdim, hinv, vinv, ncoord.as<float4>(),
+                                  S.ix_part.as<float>()));
+    HIPCHK(hipMemcpyAsync(S.ix_pin.p, S.ix_part.p, pbytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    index_finish_bounds(S.ix_pin.as<float>(), nblk, bounds);
+  }
+  div_used = div_opt > 0 ? div_opt : bin_div_density(n, bounds.alo, bounds.ahi, tdim);
+  bin_grid(bounds.lo, bounds.hi, tdim, std::sqrt(search_r2()), div_used, bins);
+  if (grid_only) return CWBL_OK;
+  const int ncell = bins.nbx * bins.nby * bins.nbz;
+  for (int i = 0; i < 2; ++i) {
+    HIPCHK(S.ix_keys[i].ensure((size_t)n * sizeof(int)));
+    HIPCHK(S.ix_vals[i].ensure((size_t)n * sizeof(int)));
+  }
+  HIPCHK(S.ix_hist.ensure((size_t)index_sort_blocks(n) * 256 * sizeof(int)));
+  if (bxyz) HIPCHK(bxyz->ensure(((size_t)n + kBinPad) * sizeof(float4)));
+  HIPCHK(bstart.ensure(((size_t)ncell + 1) * sizeof(int)));
+  int *keys[2] = {S.ix_keys[0].as<int>(), S.ix_keys[1].as<int>()};
+  int *vals[2] = {S.ix_vals[0].as<int>(), S.ix_vals[1].as<int>()};
+  const IndexGrid g{bins.x0, bins.y0, bins.z0, bins.binv, bins.nbx, bins.nby, bins.nbz};
+  int which = 0;
+  HIPCHK(launch_index_sort(s, n, ncell, ncoord.as<float4>(), tdim, g, keys, vals,
+                           S.ix_hist.as<int>(), &which));
+  HIPCHK(launch_index_finish(s, ncoord.as<float4>(), n, ncell, keys[which], vals[which],
+                             bxyz ? bxyz->as<float4>() : nullptr, bstart.as<int>()));
+  if (skeys) *skeys = keys[which];
+  if (svals) *svals = vals[which];
+  return CWBL_OK;
+}
+
+// The host worker of a mode-1 tree: build_tree's normalisation and kdtree2_create, host work
+// only (the calling thread makes every HIP call).  ot.xyz stays put until release_obs, which
+// joins the worker first.
+void start_tree_worker(TreeBufs *tb, const ObsType &ot, bool dim3) {
+  const float *xyz = ot.xyz.data();
+  const int n = ot.nobs, tdim = dim3 ? 3 : 2;
+  const float hinv = tb->hinv, vinv = tb->vinv;
+  tb->worker_started = true;
+  tb->worker_joined = false;
+  ++P.trees_built;
+  tb->worker = std::thread([tb, xyz, n, tdim, dim3, hinv, vinv] {
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<float> nx(3 * (size_t)n);
+    for (int j = 0; j < n; ++j) {
+      nx[3 * (size_t)j + 0] = xyz[3 * (size_t)j + 0] * hinv;
+      nx[3 * (size_t)j + 1] = xyz[3 * (size_t)j + 1] * hinv;
+      nx[3 * (size_t)j + 2] = dim3 ? xyz[3 * (size_t)j + 2] * vinv : -1.0f;
+    }
+    build_kdtree(nx.data(), n, tdim, tb->host);
+    tb->depth = tree_depth(tb->host);
+    tb->worker_ms = ms_since(t0);
+  });
+}
+
+// Joins a mode-1 tree's worker and uploads the tree on stream s (once).
+int ready_tree(TreeBufs *tb, hipStream_t s) {
+  if (tb->tree_ready) return CWBL_OK;
+  if (!tb->worker_joined) {
+    const auto t0 = std::chrono::steady_clock::now();
+    tb->join();
+    P.ms_tree_wait += ms_since(t0);
+    P.ms_tree += tb->worker_ms;
+  }
+  if (tb->depth >= kSearchStackDepth)
+    return fail(CWBL_ERR_UNSUPPORTED, "k-d tree too deep (%d obs)", tb->n);
+  const HostTree &h = tb->host;
+  HIPCHK(tb->nodes.ensure(std::max<size_t>(h.nodes.size(), 1) * sizeof(TreeNode)));
+  HIPCHK(tb->rdata.ensure(h.rdata.size() * sizeof(float)));
+  HIPCHK(tb->ind.ensure(h.ind.size() * sizeof(int) + 4));
+  HIPCHK(hipMemcpyAsync(tb->nodes.p, h.nodes.data(), h.nodes.size() * sizeof(TreeNode),
+                        hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(tb->rdata.p, h.rdata.data(), h.rdata.size() * sizeof(float),
+                        hipMemcpyHostToDevice, s));
+  if (!h.ind.empty())
+    HIPCHK(hipMemcpyAsync(tb->ind.p, h.ind.data(), h.ind.size() * sizeof(int),
+                          hipMemcpyHostToDevice, s));
+  tb->tree_ready = true;
+  return CWBL_OK;
+}
+
+// CWBL_OPT_INDEX = 1: the cache entry of one normalisation, its bins built on the device
+// (rebuilt alone when the divisor changes), its tree left to a worker when the type can
+// truncate (or is searched by tree walk).
+int index_entry(int entry, int tdim, bool dim3, float hinv, float vinv, int max_lz,
+                TreeBufs *&out) {
+  ObsType &ot = S.obs[entry];
+  const int n = ot.nobs;
+  TreeBufs *tb = nullptr;
+  for (auto &t : S.tree_cache)
+    if (t->mode == 1 && t->entry == entry && t->dim == tdim && t->hinv == hinv &&
+        (!dim3 || t->vinv == vinv))
+      tb = t.get();
+  const bool fresh = !tb;
+  if (fresh) {
+    auto nt = std::make_unique<TreeBufs>();
+    nt->mode = 1; nt->entry = entry; nt->dim = tdim; nt->hinv = hinv; nt->vinv = vinv;
+    nt->n = n;
+    tb = nt.get();
+    S.tree_cache.push_back(std::move(nt));
+  }
+  // the tree first: the worker builds it while the device builds the bins
+  if (!tb->worker_started && (!S.binned || n > max_lz)) start_tree_worker(tb, ot, dim3);
+  if (fresh || tb->bin_div_opt != S.bin_div) {
+    if (!ot.dxyz_ok) {
+      HIPCHK(ot.dxyz.ensure(ot.xyz.size() * sizeof(float)));
+      HIPCHK(hipMemcpyAsync(ot.dxyz.p, ot.xyz.data(), ot.xyz.size() * sizeof(float),
+                            hipMemcpyHostToDevice, S.stream));
+      ot.dxyz_ok = true;
+    }
+    HIPCHK(prep_begin(S.stream, 0));
+    if (int rc = device_bins(S.stream, ot.dxyz.as<float>(), n, tdim, hinv, vinv, S.bin_div,
+                             !fresh, tb->bounds, tb->ncoord, tb->bins, tb->bin_div_used, false,
+                             &tb->bxyz, tb->bstart))
+      return rc;
+    HIPCHK(prep_end(S.stream));
+    tb->bin_div_opt = S.bin_div;
+    ++P.bins_built;
+    ++P.bins_on_device;
+  }
+  out = tb;
+  return CWBL_OK;
 }
 
 // Builds the trees of one family (build_tree, module_localization.f90:35-167) and their
 // column tables.  Appends TreeDesc entries.
 int build_family(int family, const cwbl_var_params *vp, std::vector<TreeDesc> &descs,
-                 int &list_cap, int &max_depth) {
+                 int &list_cap, int &max_depth, std::vector<TreeBufs *> &tbs) {
   struct Pending { int entry; int type_id; const cwbl_type_params *tp; float hinv, vinv; };
   std::vector<Pending> pend;
   const int ntypes = family == 0 ? CWBL_NUM_GTS_TYPES : CWBL_NUM_RADAR_TYPES;
@@ -528,9 +733,13 @@ int build_family(int family, const cwbl_var_params *vp, std::vector<TreeDesc> &d
     const int n = ot.nobs;
     const int tdim = dim3 ? 3 : 2;
     TreeBufs *tb = nullptr;
+    if (S.index_mode == 1) {
+      if (int rc = index_entry(pd.entry, tdim, dim3, pd.hinv, pd.vinv, pd.tp->max_lz_pts, tb))
+        return rc;
+    }
     for (auto &t : S.tree_cache)
-      if (t->entry == pd.entry && t->dim == tdim && t->hinv == pd.hinv &&
-          (!dim3 || t->vinv == pd.vinv) && t->bin_div_opt == S.bin_div)
+      if (S.index_mode == 0 && t->mode == 0 && t->entry == pd.entry && t->dim == tdim &&
+          t->hinv == pd.hinv && (!dim3 || t->vinv == pd.vinv) && t->bin_div_opt == S.bin_div)
         tb = t.get();
     if (!tb) {  // build_tree (:35-167) for this normalisation
       std::vector<float> nx(3 * (size_t)n);
@@ -542,8 +751,12 @@ int build_family(int family, const cwbl_var_params *vp, std::vector<TreeDesc> &d
       auto nt = std::make_unique<TreeBufs>();
       nt->entry = pd.entry; nt->dim = tdim; nt->hinv = pd.hinv; nt->vinv = pd.vinv;
       nt->bin_div_opt = S.bin_div;
+      nt->n = n;
+      const auto t_tree = std::chrono::steady_clock::now();
       build_kdtree(nx.data(), n, tdim, nt->host);
       nt->depth = tree_depth(nt->host);
+      P.ms_tree += ms_since(t_tree);
+      ++P.trees_built;
       if (nt->depth >= kSearchStackDepth)
         return fail(CWBL_ERR_UNSUPPORTED, "k-d tree too deep (%d obs)", n);
       const HostTree &h = nt->host;
@@ -557,7 +770,10 @@ int build_family(int family, const cwbl_var_params *vp, std::vector<TreeDesc> &d
       if (!h.ind.empty())
         HIPCHK(hipMemcpyAsync(nt->ind.p, h.ind.data(), h.ind.size() * sizeof(int),
                               hipMemcpyHostToDevice, S.stream));
+      const auto t_bins = std::chrono::steady_clock::now();
       build_bins(h, tdim, std::sqrt(search_r2()), nt->bins, bin_div_for(h, tdim));
+      P.ms_bins += ms_since(t_bins);
+      ++P.bins_built;
       const HostBins &hb = nt->bins;
       // (+ kBinPad points: search_binned_kernel reads up to 7 points past a run's end)
       HIPCHK(nt->bxyz.ensure(hb.xyzs.size() * sizeof(float) + 16 * kBinPad));
@@ -583,15 +799,23 @@ int build_family(int family, const cwbl_var_params *vp, std::vector<TreeDesc> &d
     } else {
       is_assim[0] = tp->hclr > 0.0f ? 1 : 0;
     }
+    // (index mode 1: a slot is the obs index, the columns stay in obs order)
+    HIPCHK(prep_begin(S.stream, 1));
     HIPCHK(launch_obs_prep(S.stream, S.k, S.kp, family, ot.type_id, ot.nvar, n,
                            ot.obs.as<float>(), ot.error.as<float>(), ot.hdxb.as<float>(),
                            ot.qc.as<int>(), tp->err_muti, tp->err_rej, is_assim, S.norain,
-                           tb->ind.as<int>(), tb->col_bg.as<float>(), tb->col_omm.as<float>(),
-                           tb->col_err.as<float>(), tb->col_ok.as<uint8_t>()));
+                           tb->mode == 1 ? nullptr : tb->ind.as<int>(), tb->col_bg.as<float>(),
+                           tb->col_omm.as<float>(), tb->col_err.as<float>(),
+                           tb->col_ok.as<uint8_t>()));
+    HIPCHK(prep_end(S.stream));
     TreeDesc d{};
-    d.nodes = tb->nodes.as<TreeNode>();
-    d.rdata = tb->rdata.as<float4>();
-    d.ind = tb->ind.as<int>();
+    if (tb->mode == 1) {  // the solve's table: coordinates by obs index, no tree
+      d.rdata = tb->ncoord.as<float4>();
+    } else {
+      d.nodes = tb->nodes.as<TreeNode>();
+      d.rdata = tb->rdata.as<float4>();
+      d.ind = tb->ind.as<int>();
+    }
     d.col_bg = tb->col_bg.as<float>();
     d.col_omm = tb->col_omm.as<float>();
     d.col_err = tb->col_err.as<float>();
@@ -609,8 +833,9 @@ int build_family(int family, const cwbl_var_params *vp, std::vector<TreeDesc> &d
     d.bx0 = tb->bins.x0; d.by0 = tb->bins.y0; d.bz0 = tb->bins.z0; d.binv = tb->bins.binv;
     d.nbx = tb->bins.nbx; d.nby = tb->bins.nby; d.nbz = tb->bins.nbz;
     list_cap += list_span(tp->max_lz_pts);
-    max_depth = std::max(max_depth, tb->depth);
+    if (tb->mode == 0) max_depth = std::max(max_depth, tb->depth);
     descs.push_back(d);
+    tbs.push_back(tb);
   }
   return CWBL_OK;
 }
@@ -619,7 +844,7 @@ void release_obs() {
   for (auto &t : S.tree_cache) t->release();
   S.tree_cache.clear();
   for (auto &o : S.obs) {
-    o.obs.release(); o.error.release(); o.hdxb.release(); o.qc.release();
+    o.obs.release(); o.error.release(); o.hdxb.release(); o.qc.release(); o.dxyz.release();
   }
   S.obs.clear();
   S.have_obs = false;
@@ -631,8 +856,15 @@ void release_all() {
   S.cevents.clear();
   for (DevBuf *b : {&S.tdesc, &S.nbr_cnt, &S.nbr_idx, &S.nbr_cnt2, &S.nbr_idx2, &S.info, &S.stats, &S.sx,
                     &S.sy, &S.salt, &S.svar, &S.bcol, &S.byo, &S.byb, &S.bxb, &S.bxa, &S.bev, &S.btri,
-                    &S.qxyz, &S.qnf, &S.qidx, &S.qr2, &S.quad, &S.wsa, &S.flags})
+                    &S.qxyz, &S.qnf, &S.qidx, &S.qr2, &S.quad, &S.wsa, &S.flags, &S.tdesc_tree,
+                    &S.ix_keys[0], &S.ix_keys[1], &S.ix_vals[0], &S.ix_vals[1], &S.ix_hist,
+                    &S.ix_part})
     b->release();
+  S.ix_pin.release();
+  for (hipEvent_t e : S.pevents) (void)hipEventDestroy(e);
+  S.pevents.clear();
+  g_pspans.clear();
+  g_pev_used = 0;
   for (hipEvent_t e : S.events) (void)hipEventDestroy(e);
   S.events.clear();
   for (hipEvent_t e : S.kevents) (void)hipEventDestroy(e);
@@ -712,6 +944,10 @@ struct VarCall {
   // through the library's page-locked bounce slots
   bool host = false, piped = false, piped_back = false, bounce = false, registered = false;
   std::vector<TreeDesc> descs;
+  // index mode 1: the cache entry of every descriptor, and whether the tree searches' table
+  // (S.tdesc_tree: the trees that exist, with their own rdata) has been uploaded
+  std::vector<TreeBufs *> tbs;
+  bool index1 = false, trees_ready = false;
   int list_cap = 0, max_depth = 1, nt = 0;
   std::vector<std::pair<long long, int>> plan;  // (g0, nb)
   long long B = 0, Bc = 0, info_cap = 0, win0 = 0;
@@ -725,14 +961,42 @@ struct VarCall {
 };
 
 // build_tree of both families and the upload of their descriptors (nt = 0: nothing to do)
+// Index mode 1, when a search first needs the trees: join the workers of the types that have
+// one, upload the trees and the tree searches' descriptor table on stream s, raise max_depth.
+// (A second table: the solves in flight keep reading S.tdesc.)
+int ready_trees(VarCall &v, hipStream_t s) {
+  if (v.trees_ready) return CWBL_OK;
+  std::vector<TreeDesc> sd = v.descs;
+  for (size_t i = 0; i < sd.size(); ++i) {
+    TreeBufs *tb = v.tbs[i];
+    if (!tb->worker_started) continue;  // cannot truncate: nodes stays null
+    if (int rc = ready_tree(tb, s)) return rc;
+    sd[i].nodes = tb->nodes.as<TreeNode>();
+    sd[i].rdata = tb->rdata.as<float4>();
+    sd[i].ind = tb->ind.as<int>();
+    v.max_depth = std::max(v.max_depth, tb->depth);
+  }
+  HIPCHK(S.tdesc_tree.ensure(sd.size() * sizeof(TreeDesc)));
+  // (from pageable memory: the copy has left `sd` when the call returns)
+  HIPCHK(hipMemcpyAsync(S.tdesc_tree.p, sd.data(), sd.size() * sizeof(TreeDesc),
+                        hipMemcpyHostToDevice, s));
+  HIPCHK(hipStreamSynchronize(s));
+  v.trees_ready = true;
+  return CWBL_OK;
+}
+
 int plan_trees(VarCall &v) {
-  if (int rc = build_family(0, v.vp, v.descs, v.list_cap, v.max_depth)) return rc;
-  if (int rc = build_family(1, v.vp, v.descs, v.list_cap, v.max_depth)) return rc;
+  v.index1 = S.index_mode == 1;
+  if (int rc = build_family(0, v.vp, v.descs, v.list_cap, v.max_depth, v.tbs)) return rc;
+  if (int rc = build_family(1, v.vp, v.descs, v.list_cap, v.max_depth, v.tbs)) return rc;
   v.nt = (int)v.descs.size();
   if (v.nt == 0 || v.npts == 0) return CWBL_OK;
   HIPCHK(S.tdesc.ensure(v.descs.size() * sizeof(TreeDesc)));
   HIPCHK(hipMemcpyAsync(S.tdesc.p, v.descs.data(), v.descs.size() * sizeof(TreeDesc),
                         hipMemcpyHostToDevice, S.stream));
+  // the tree walk for every point needs every tree at once
+  if (v.index1 && !S.binned)
+    if (int rc = ready_trees(v, S.stream)) return rc;
   return CWBL_OK;
 }
 
@@ -934,10 +1198,33 @@ int search_batch(VarCall &v, long long bi, int *ncnt, int *nidx, hipEvent_t a, h
     HIPCHK(launch_search_binned(ss, dtrees, v.nt, v.list_cap, v.c.r2, v.rbox, v.sd, g0, nb, ncnt,
                                 nidx, fcnt, fidx));
     HIPCHK(kt_end(ss, kt, KT_SEARCH_BINNED, nb));
+    if (v.index1) {
+      // the batch's flag count, waited for on the search stream only (the previous batch's
+      // solve is already queued on S.stream): no flagged point, no tree search and no tree
+      HIPCHK(S.ix_pin.ensure(64));
+      int *hcnt = S.ix_pin.as<int>();
+      HIPCHK(hipMemcpyAsync(hcnt, fcnt, sizeof(int), hipMemcpyDeviceToHost, ss));
+      HIPCHK(hipStreamSynchronize(ss));
+      if (*hcnt > 0) {
+        ++P.flagged_batches;
+        if (int rc = ready_trees(v, ss)) return rc;
+        HIPCHK(kt_begin(ss, &kt));
+        HIPCHK(launch_search_flagged(ss, S.tdesc_tree.as<TreeDesc>(), v.nt, v.max_depth,
+                                     v.list_cap, v.c.r2, v.sd, g0, nb, fcnt, fidx, ncnt, nidx,
+                                     dst, true));
+        HIPCHK(kt_end(ss, kt, KT_SEARCH_FLAGGED, 0));
+      }
+    } else {
+      HIPCHK(kt_begin(ss, &kt));
+      HIPCHK(launch_search_flagged(ss, dtrees, v.nt, v.max_depth, v.list_cap, v.c.r2, v.sd, g0,
+                                   nb, fcnt, fidx, ncnt, nidx, dst));
+      HIPCHK(kt_end(ss, kt, KT_SEARCH_FLAGGED, 0));
+    }
+  } else if (v.index1) {
     HIPCHK(kt_begin(ss, &kt));
-    HIPCHK(launch_search_flagged(ss, dtrees, v.nt, v.max_depth, v.list_cap, v.c.r2, v.sd, g0, nb,
-                                 fcnt, fidx, ncnt, nidx, dst));
-    HIPCHK(kt_end(ss, kt, KT_SEARCH_FLAGGED, 0));
+    HIPCHK(launch_search(ss, S.tdesc_tree.as<TreeDesc>(), v.nt, v.max_depth, v.list_cap, v.c.r2,
+                         v.sd, g0, nb, ncnt, nidx, nullptr, dst, true));
+    HIPCHK(kt_end(ss, kt, KT_SEARCH_TREE, nb));
   } else {
     HIPCHK(kt_begin(ss, &kt));
     HIPCHK(launch_search(ss, dtrees, v.nt, v.max_depth, v.list_cap, v.c.r2, v.sd, g0, nb, ncnt,
@@ -1131,6 +1418,7 @@ int finish_call(VarCall &v, cwbl_stats &st) {
   HIPCHK(hipMemcpyAsync(&ds, S.stats.p, sizeof ds, hipMemcpyDeviceToHost, S.stream));
   HIPCHK(hipStreamSynchronize(S.stream));
   kt_collect();
+  prep_collect();
 
   st.solved = (long long)ds.solved;
   st.nobs_sum = (long long)ds.nobs_sum;
@@ -1226,6 +1514,8 @@ int cwbl_init(const cwbl_init_params *p) {
   S.binned = true;
   S.pageable_register = true;
   S.bin_div = 0;  // 0: by density (bin_div_for)
+  S.index_mode = 0;
+  std::memset(&P, 0, sizeof P);
   S.lead_div = 0;
   S.serial_search = false;
 #ifdef CWBL_DEBUG_KNOBS
@@ -1292,6 +1582,10 @@ int cwbl_set_option(int option, long long value) {
     case CWBL_OPT_INFO_WINDOW:
       if (value != 0 && !range(256, 1LL << 30)) break;
       S.info_window = value ? value : (1LL << 25);
+      return CWBL_OK;
+    case CWBL_OPT_INDEX:
+      if (!range(0, 1)) break;
+      S.index_mode = (int)value;
       return CWBL_OK;
     default:
       return fail(CWBL_ERR_ARG, "cwbl_set_option: unknown option %d", option);
@@ -1419,6 +1713,9 @@ int cwbl_analyze_var(const cwbl_var_params *vp, const cwbl_slab *sl, cwbl_stats 
   S.kpend.clear();  // (an earlier call that failed midway leaves nothing to collect)
   S.kev_used = 0;
   g_bounce_ms = 0.0;
+  std::memset(&P, 0, sizeof P);
+  g_pspans.clear();
+  g_pev_used = 0;
   cwbl_stats st;
   std::memset(&st, 0, sizeof st);
   const long long npts = (long long)sl->ix_lim * sl->iy_lim * sl->nz;
@@ -1455,6 +1752,7 @@ int cwbl_analyze_var(const cwbl_var_params *vp, const cwbl_slab *sl, cwbl_stats 
   st.ntrees = v.nt;
   if (v.nt == 0 || npts == 0) {  // `if(all(.not. succeed)) cycle` (:66)
     HIPCHK(hipStreamSynchronize(S.stream));
+    prep_collect();
     return finish();
   }
   for (const TreeDesc &d : v.descs) st.q1_undefined += d.q1_undef ? npts : 0;
@@ -1735,6 +2033,74 @@ int cwbl_search(int nobs, const float *obs_xyz, float hclr, float vclr, int max_
   HIPCHK(hipStreamSynchronize(S.stream));
   dd.release();
   tb.nodes.release(); tb.rdata.release(); tb.ind.release();
+  return CWBL_OK;
+}
+
+int cwbl_bin_index(int nobs, const float *obs_xyz, float hclr, float vclr, int div,
+                   cwbl_bin_grid *grid, long long start_cap, int *start, int *order,
+                   int memory) {
+  if (int rc = require_device()) return rc;
+  if (nobs < 0 || !(hclr > 0.0f) || div < 0 || div > 8 || !grid || (nobs > 0 && !obs_xyz) ||
+      (memory != CWBL_MEM_HOST && memory != CWBL_MEM_DEVICE) ||
+      (start && nobs > 0 && !order))
+    return fail(CWBL_ERR_ARG, "cwbl_bin_index: bad arguments");
+  const float hinv = 1.0f / (hclr * 1e3f);
+  const float vinv = vclr > 0.0f ? 1.0f / (vclr * 1e3f) : -1.0f;
+  const int tdim = vinv > 0.0f ? 3 : 2;
+  if (memory == CWBL_MEM_DEVICE) HIPCHK(order_after_caller());
+  HostBins bins;
+  int div_used = div > 0 ? div : 2;
+  DevBuf dxyz, ncoord, bstart;
+  struct Free {
+    DevBuf &a, &b, &c;
+    ~Free() { a.release(); b.release(); c.release(); }
+  } fr{dxyz, ncoord, bstart};
+  const int *svals = nullptr;
+  auto out_grid = [&]() {
+    grid->x0 = bins.x0; grid->y0 = bins.y0; grid->z0 = bins.z0; grid->binv = bins.binv;
+    grid->nbx = bins.nbx; grid->nby = bins.nby; grid->nbz = bins.nbz; grid->div = div_used;
+  };
+  const auto d2 = memory == CWBL_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  if (nobs == 0) {  // the grid of no point: one cell
+    const float z[3] = {0.0f, 0.0f, 0.0f};
+    bin_grid(z, z, tdim, std::sqrt(search_r2()), div_used, bins);
+    out_grid();
+    if (!start) return CWBL_OK;
+    if (start_cap < 2) return fail(CWBL_ERR_ARG, "cwbl_bin_index: start holds %lld < 2", start_cap);
+    HIPCHK(bstart.ensure(2 * sizeof(int)));
+    HIPCHK(hipMemsetAsync(bstart.p, 0, 2 * sizeof(int), S.stream));
+    HIPCHK(hipMemcpyAsync(start, bstart.p, 2 * sizeof(int), d2, S.stream));
+    HIPCHK(hipStreamSynchronize(S.stream));
+    return CWBL_OK;
+  }
+  const float *dx = obs_xyz;
+  if (memory != CWBL_MEM_DEVICE) {
+    HIPCHK(stage(dxyz, obs_xyz, (size_t)nobs * 12, CWBL_MEM_HOST));
+    dx = dxyz.as<float>();
+  }
+  IndexBounds bounds{};
+  if (int rc = device_bins(S.stream, dx, nobs, tdim, hinv, vinv, div, false, bounds, ncoord, bins,
+                           div_used, true, nullptr, bstart))
+    return rc;
+  out_grid();
+  if (!start) return CWBL_OK;
+  const long long ncell = (long long)bins.nbx * bins.nby * bins.nbz;
+  if (start_cap < ncell + 1)
+    return fail(CWBL_ERR_ARG, "cwbl_bin_index: start holds %lld < %lld entries", start_cap,
+                ncell + 1);
+  if (int rc = device_bins(S.stream, dx, nobs, tdim, hinv, vinv, div, true, bounds, ncoord, bins,
+                           div_used, false, nullptr, bstart, nullptr, &svals))
+    return rc;
+  HIPCHK(hipMemcpyAsync(start, bstart.p, (size_t)(ncell + 1) * sizeof(int), d2, S.stream));
+  HIPCHK(hipMemcpyAsync(order, svals, (size_t)nobs * sizeof(int), d2, S.stream));
+  HIPCHK(hipStreamSynchronize(S.stream));
+  return CWBL_OK;
+}
+
+int cwbl_prep_info(cwbl_prep_info_t *out) {
+  if (int rc = require_device()) return rc;
+  if (!out) return fail(CWBL_ERR_ARG, "cwbl_prep_info: null argument");
+  *out = P;
   return CWBL_OK;
 }
 

@@ -41,7 +41,9 @@ struct TreeDesc {
   const float4   *rdata;      // rearranged normalised coords (x,y,z,0)
   const int      *ind;
   // column table of this type for the current variable, one column per (tree slot,
-  // obs-var): column slot*nvar + v belongs to obs ind[slot]
+  // obs-var): column slot*nvar + v belongs to obs ind[slot].  With the device-built index
+  // (CWBL_OPT_INDEX = 1) a slot is the obs index itself: the solve's table then has rdata in
+  // obs order, and the tree searches get a second table with the tree's own rdata.
   const float    *col_bg;     // [n*nvar][KP] fp32 bg = hdxb - mean, zero padded
   const float    *col_omm;    // [n*nvar] obs - mean
   const float    *col_err;    // [n*nvar] error * err_muti
@@ -73,6 +75,36 @@ struct HostBins {
 // Bins of side ~r/2 (r: the search radius in normalised units) over a built tree's
 // rearranged coordinates; dim 2 ignores z.  Capped at 2^22 cells.
 void build_bins(const HostTree &t, int dim, float r, HostBins &out, int div = 2);
+// The grid of build_bins from the coordinates' bounds (lo/hi per coordinate over its finite
+// values, 0 where there is none): cell side h = r / div, grown by 1.25 until the grid has at
+// most 2^22 cells; fills x0..nbz of `out`.  Shared by the host and the device bin builds.
+void bin_grid(const float lo[3], const float hi[3], int dim, float r, int div, HostBins &out);
+
+// ---- device bin build (cwbl_index.hip; CWBL_OPT_INDEX = 1 and cwbl_bin_index) ----------------
+struct IndexGrid {  // HostBins' grid as the kernels take it
+  float x0, y0, z0, binv;
+  int nbx, nby, nbz;
+};
+constexpr int kIndexBoundWords = 12;
+struct IndexBounds {
+  float lo[3], hi[3];    // per coordinate over its finite values (build_bins), 0 if none
+  float alo[3], ahi[3];  // over the points whose coordinates are all finite (bin_div_for)
+  bool aseen;            // there is such a point
+};
+int index_bound_blocks(int n);  // blocks of launch_index_normalize: kIndexBoundWords floats each
+int index_sort_blocks(int n);   // blocks of a sort pass: 256 ints of `hist` each
+// xyz(3,n) -> ncoord[n] = (x hinv, y hinv, dim 3 ? z vinv : 0, 0) and the blocks' partial bounds
+hipError_t launch_index_normalize(hipStream_t s, const float *xyz, int n, int dim, float hinv,
+                                  float vinv, float4 *ncoord, float *part);
+void index_finish_bounds(const float *part, int nblocks, IndexBounds &b);  // host
+// cell ids of ncoord on grid g, then the stable sort of (cell id, obs index) by cell id:
+// keys/vals are two buffers of n ints each, the result is in keys[*which], vals[*which]
+hipError_t launch_index_sort(hipStream_t s, int n, int ncell, const float4 *ncoord, int dim,
+                             IndexGrid g, int *keys[2], int *vals[2], int *hist, int *which);
+// bstart[0..ncell] from the sorted cell ids and (bxyz non-null) the bin payload of n + kBinPad
+// points
+hipError_t launch_index_finish(hipStream_t s, const float4 *ncoord, int n, int ncell,
+                               const int *skeys, const int *svals, float4 *bxyz, int *bstart);
 
 // Per-variable constants of the solve.
 struct SolveConsts {
@@ -179,10 +211,14 @@ hipError_t launch_scale(hipStream_t s, float *x, long long n, float alpha);
 // letkf_tune_q over the analysed region of s.var (module_letkf_core.f90:702-733)
 hipError_t launch_tune_q(hipStream_t st, SlabDev s, int k);
 
-// depth: the deepest tree's level count (tree_depth), which sizes the traversal stacks
+// depth: the deepest tree's level count (tree_depth), which sizes the traversal stacks.
+// obs_slots (CWBL_OPT_INDEX = 1): the columns are numbered by obs index, so the analysis lists
+// get ind[slot] instead of the tree slot, and a type without a tree (nodes == nullptr: it
+// cannot truncate) keeps the list the binned search wrote.
 hipError_t launch_search(hipStream_t s, const TreeDesc *trees, int ntrees, int depth,
                          int list_cap, float r2, SlabDev slab, long long g0, int npts,
-                         int *nbr_cnt, int *nbr_idx, float *nbr_r2, DevStats *stats);
+                         int *nbr_cnt, int *nbr_idx, float *nbr_r2, DevStats *stats,
+                         bool obs_slots = false);
 
 // nbr_idx holds tree slots (search with nbr_r2 = nullptr); the solve recomputes r2
 hipError_t launch_solve_neighbors(hipStream_t s, int kp, const TreeDesc *trees,
@@ -282,7 +318,7 @@ hipError_t launch_search_binned(hipStream_t s, const TreeDesc *trees, int ntrees
 hipError_t launch_search_flagged(hipStream_t s, const TreeDesc *trees, int ntrees, int depth,
                                  int list_cap, float r2, SlabDev slab, long long g0, int npts,
                                  const int *flag_cnt, const int *flag_idx, int *nbr_cnt,
-                                 int *nbr_idx, DevStats *stats);
+                                 int *nbr_idx, DevStats *stats, bool obs_slots = false);
 
 hipError_t launch_search_single(hipStream_t s, const TreeDesc *tree, int depth, float r2,
                                 int nq, const float *q_xyz, int max_lz, int *nfound, int *idx,

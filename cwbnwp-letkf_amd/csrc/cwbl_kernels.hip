@@ -126,6 +126,8 @@ __device__ __forceinline__ float dis2_from_bnd(float x, float amin, float amax) 
 // decision to visit the farther child can be taken before descending the closer one, and
 // LIFO order then reproduces the recursive visiting order exactly.
 constexpr int kAhead = 4;  // bucket points loaded ahead of their tests
+// OBS (CWBL_OPT_INDEX = 1): the analysis lists hold obs indices (ind[slot]), not tree slots
+template <bool OBS>
 __device__ int search_tree(const TreeDesc &T, float q0, float q1, float q2, float r2,
                            int *out_idx, float *out_r2, int *stk, bool &overflow) {
   const TreeNode *__restrict__ nodes = T.nodes;
@@ -196,10 +198,11 @@ __device__ int search_tree(const TreeDesc &T, float q0, float q1, float q2, floa
             out_r2[count] = sd;
           } else {       // analysis: the tree slot (columns are stored in slot order)
             const int g = count % kListGroup;
-            grp.x = g == 0 ? i : grp.x;
-            grp.y = g == 1 ? i : grp.y;
-            grp.z = g == 2 ? i : grp.z;
-            grp.w = i;
+            const int o = OBS ? T.ind[i] : i;
+            grp.x = g == 0 ? o : grp.x;
+            grp.y = g == 1 ? o : grp.y;
+            grp.z = g == 2 ? o : grp.z;
+            grp.w = o;
             if (g == kListGroup - 1)
               *reinterpret_cast<int4 *>(out_idx + list_slot(count - g)) = grp;
           }
@@ -255,7 +258,7 @@ struct FlagQuery {
   __device__ void at(int gi, float &x, float &y, float &z) const { sq.at(gi, x, y, z); }
 };
 
-template <class Q>
+template <class Q, bool OBS = false>
 __global__ void __launch_bounds__(64)
 search_kernel(const TreeDesc *__restrict__ trees, int ntrees, int list_cap, float r2, Q qs,
               int npts, int *__restrict__ nbr_cnt, int *__restrict__ nbr_idx,
@@ -279,8 +282,11 @@ search_kernel(const TreeDesc *__restrict__ trees, int ntrees, int list_cap, floa
                                   : list_index(gi, list_cap, T.list_off);
     bool ovf = false;
     int cnt = 0;
+    if constexpr (OBS) {
+      if (!T.nodes) continue;  // no tree: the type cannot truncate, its binned list stands
+    }
     if (T.max_lz > 0)
-      cnt = search_tree(T, q0, q1, q2, r2, nbr_idx + base, nbr_r2 ? nbr_r2 + base : nullptr,
+      cnt = search_tree<OBS>(T, q0, q1, q2, r2, nbr_idx + base, nbr_r2 ? nbr_r2 + base : nullptr,
                         stk + threadIdx.x, ovf);
     nbr_cnt[(long long)gi * ntrees + t] = cnt;
     trunc += ovf ? 1u : 0u;
@@ -294,9 +300,16 @@ static size_t stack_bytes(int depth) {
 
 hipError_t launch_search(hipStream_t s, const TreeDesc *trees, int ntrees, int depth,
                          int list_cap, float r2, SlabDev slab, long long g0, int npts,
-                         int *nbr_cnt, int *nbr_idx, float *nbr_r2, DevStats *stats) {
+                         int *nbr_cnt, int *nbr_idx, float *nbr_r2, DevStats *stats,
+                         bool obs_slots) {
   if (npts <= 0) return hipSuccess;
   SlabQuery q{slab, g0};
+  if (obs_slots) {
+    hipLaunchKernelGGL((search_kernel<SlabQuery, true>), dim3((npts + 63) / 64), dim3(64),
+                       stack_bytes(depth), s, trees, ntrees, list_cap, r2, q, npts, nbr_cnt,
+                       nbr_idx, nbr_r2, stats);
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL(search_kernel<SlabQuery>, dim3((npts + 63) / 64), dim3(64),
                      stack_bytes(depth), s, trees,
                      ntrees, list_cap, r2, q, npts, nbr_cnt, nbr_idx, nbr_r2, stats);
@@ -442,9 +455,15 @@ hipError_t launch_search_binned(hipStream_t s, const TreeDesc *trees, int ntrees
 hipError_t launch_search_flagged(hipStream_t s, const TreeDesc *trees, int ntrees, int depth,
                                  int list_cap, float r2, SlabDev slab, long long g0, int npts,
                                  const int *flag_cnt, const int *flag_idx, int *nbr_cnt,
-                                 int *nbr_idx, DevStats *stats) {
+                                 int *nbr_idx, DevStats *stats, bool obs_slots) {
   if (npts <= 0) return hipSuccess;
   FlagQuery q{SlabQuery{slab, g0}, flag_cnt, flag_idx};
+  if (obs_slots) {
+    hipLaunchKernelGGL((search_kernel<FlagQuery, true>), dim3((npts + 63) / 64), dim3(64),
+                       stack_bytes(depth), s, trees, ntrees, list_cap, r2, q, npts, nbr_cnt,
+                       nbr_idx, (float *)nullptr, stats);
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL(search_kernel<FlagQuery>, dim3((npts + 63) / 64), dim3(64),
                      stack_bytes(depth), s, trees, ntrees, list_cap, r2, q, npts, nbr_cnt,
                      nbr_idx, (float *)nullptr, stats);

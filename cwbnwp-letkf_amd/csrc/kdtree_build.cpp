@@ -118,6 +118,23 @@ void build_kdtree(const float *xyz3, int n, int dim, HostTree &out) {
       out.rdata[4 * static_cast<size_t>(i) + d] = d < dim ? xyz3[3 * out.ind[i] + d] : 0.0f;
 }
 
+void bin_grid(const float lo_in[3], const float hi_in[3], int dim, float r, int div,
+              HostBins &out) {
+  float lo[3] = {lo_in[0], lo_in[1], lo_in[2]}, hi[3] = {hi_in[0], hi_in[1], hi_in[2]};
+  if (dim < 3) lo[2] = hi[2] = 0.0f;
+  float h = r / (float)std::max(div, 1);  // cell side r / div (div 2: the ball's box spans ~5 cells)
+  long long nb[3];
+  for (;;) {
+    for (int c = 0; c < 3; ++c)
+      nb[c] = 1 + (long long)std::min(std::floor(((double)hi[c] - (double)lo[c]) / h), 4194304.0);
+    if (nb[0] * nb[1] * nb[2] <= (1LL << 22)) break;
+    h *= 1.25f;
+  }
+  out.x0 = lo[0]; out.y0 = lo[1]; out.z0 = lo[2];
+  out.binv = 1.0f / h;
+  out.nbx = (int)nb[0]; out.nby = (int)nb[1]; out.nbz = (int)nb[2];
+}
+
 void build_bins(const HostTree &t, int dim, float r, HostBins &out, int div) {
   const int n = t.n;
   out = HostBins{};
@@ -134,17 +151,8 @@ void build_bins(const HostTree &t, int dim, float r, HostBins &out, int div) {
       seen[c] = true;
     }
   if (dim < 3) lo[2] = hi[2] = 0.0f;
-  float h = r / (float)std::max(div, 1);  // cell side r / div (div 2: the ball's box spans ~5 cells)
-  long long nb[3];
-  for (;;) {
-    for (int c = 0; c < 3; ++c)
-      nb[c] = 1 + (long long)std::min(std::floor(((double)hi[c] - (double)lo[c]) / h), 4194304.0);
-    if (nb[0] * nb[1] * nb[2] <= (1LL << 22)) break;
-    h *= 1.25f;
-  }
-  out.x0 = lo[0]; out.y0 = lo[1]; out.z0 = lo[2];
-  out.binv = 1.0f / h;
-  out.nbx = (int)nb[0]; out.nby = (int)nb[1]; out.nbz = (int)nb[2];
+  bin_grid(lo, hi, dim, r, div, out);
+  const long long nb[3] = {out.nbx, out.nby, out.nbz};
   // the kernel's cell arithmetic, in fp32 (monotone, so the query's conservative box
   // brackets every cell a point within r can fall in)
   auto cell = [&](int c, float v) {

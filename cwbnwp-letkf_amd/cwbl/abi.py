@@ -28,12 +28,12 @@ GTS_NVAR = {GTS_SOUND: 4, GTS_SYNOP: 5, GTS_GPSPW: 1, GTS_METAR: 5, GTS_SHIPS: 5
 #: cwbl_set_option options (include/cwb_letkf_core.h)
 OPT_SOLVER, OPT_SPLIT40, OPT_SPLIT40_BATCH, OPT_SEARCH = 1, 2, 3, 5
 OPT_BIG_PATH, OPT_BIG_BATCH, OPT_PAGEABLE, OPT_BIN_DIV, OPT_LEAD_DIV, OPT_MAX_BATCH = 6, 7, 8, 9, 10, 11
-OPT_INFO_WINDOW = 12
+OPT_INFO_WINDOW, OPT_INDEX = 12, 13
 OPTIONS = {"solver": OPT_SOLVER, "split40": OPT_SPLIT40, "split40_batch": OPT_SPLIT40_BATCH,
            "search": OPT_SEARCH,
            "big_path": OPT_BIG_PATH, "big_batch": OPT_BIG_BATCH, "pageable": OPT_PAGEABLE,
            "bin_div": OPT_BIN_DIV, "lead_div": OPT_LEAD_DIV, "max_batch": OPT_MAX_BATCH,
-           "info_window": OPT_INFO_WINDOW}
+           "info_window": OPT_INFO_WINDOW, "index": OPT_INDEX}
 
 ERRORS = {1: "CWBL_ERR_ARG", 2: "CWBL_ERR_STATE", 3: "CWBL_ERR_NO_DEVICE", 4: "CWBL_ERR_HIP",
           5: "CWBL_ERR_UNSUPPORTED", 6: "CWBL_ERR_OOM"}
@@ -98,11 +98,26 @@ class KernelTime(C.Structure):
                 ("ms", C.c_double)]
 
 
+class BinGrid(C.Structure):
+    _fields_ = [("x0", C.c_float), ("y0", C.c_float), ("z0", C.c_float), ("binv", C.c_float),
+                ("nbx", C.c_int), ("nby", C.c_int), ("nbz", C.c_int), ("div", C.c_int)]
+
+
+class PrepInfo(C.Structure):
+    _fields_ = [("trees_built", C.c_int), ("bins_built", C.c_int), ("bins_on_device", C.c_int),
+                ("flagged_batches", C.c_int), ("ms_tree", C.c_double), ("ms_bins", C.c_double),
+                ("ms_columns", C.c_double), ("ms_tree_wait", C.c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 #: exported symbols of the product library (include/cwb_letkf_core.h)
 EXPORTS = ["cwbl_init", "cwbl_set_stream", "cwbl_set_obs", "cwbl_analyze_var", "cwbl_solve_batch", "cwbl_search",
            "cwbl_pack_columns", "cwbl_unpack_columns", "cwbl_pack_members",
            "cwbl_unpack_members", "cwbl_vcoord_mean", "cwbl_member_sum", "cwbl_scale", "cwbl_set_kernel_timing", "cwbl_kernel_times",
-           "cwbl_set_option", "cwbl_finalize", "cwbl_last_error", "cwbl_abi_version"]
+           "cwbl_set_option", "cwbl_bin_index", "cwbl_prep_info",
+           "cwbl_finalize", "cwbl_last_error", "cwbl_abi_version"]
 
 
 def _ptr(a):
@@ -281,6 +296,9 @@ def load_library(path=None):
     lib.cwbl_set_kernel_timing.argtypes = [C.c_int]
     lib.cwbl_kernel_times.argtypes = [C.POINTER(KernelTime), C.c_int, C.POINTER(C.c_int)]
     lib.cwbl_set_option.argtypes = [C.c_int, C.c_longlong]
+    lib.cwbl_bin_index.argtypes = [C.c_int, vp, C.c_float, C.c_float, C.c_int, C.POINTER(BinGrid),
+                                   C.c_longlong, vp, vp, C.c_int]
+    lib.cwbl_prep_info.argtypes = [C.POINTER(PrepInfo)]
     lib.cwbl_finalize.argtypes = []
     lib.cwbl_last_error.restype = cp
     lib.cwbl_abi_version.restype = C.c_int
@@ -288,7 +306,7 @@ def load_library(path=None):
                "cwbl_search", "cwbl_pack_columns", "cwbl_unpack_columns", "cwbl_pack_members",
                "cwbl_unpack_members", "cwbl_vcoord_mean",
                "cwbl_member_sum", "cwbl_scale", "cwbl_set_kernel_timing", "cwbl_kernel_times",
-               "cwbl_set_option", "cwbl_finalize"):
+               "cwbl_set_option", "cwbl_bin_index", "cwbl_prep_info", "cwbl_finalize"):
         getattr(lib, fn).restype = C.c_int
     return lib
 
@@ -360,6 +378,39 @@ class Core:
                                          max_lz_pts, nq, _ptr(q_xyz), _ptr(nf), _ptr(idx),
                                          _ptr(r2), MEM_HOST))
         return nf, idx, r2
+
+    def bin_index(self, obs_xyz, hclr, vclr, div=0, grid_only=False, memory=MEM_HOST):
+        """cwbl_bin_index: the device-built uniform bins of one obs type, obs_xyz (nobs,3) in
+        metres.  Returns (grid, start, order): the BinGrid, start (ncell + 1) and order (nobs)
+        as int32 numpy arrays (torch tensors for MEM_DEVICE); grid_only: (grid, None, None)."""
+        if memory == MEM_HOST:
+            obs_xyz = _f4(obs_xyz)
+        nobs = int(obs_xyz.shape[0])
+        if nobs:
+            check_array(obs_xyz, "f4", memory, "obs_xyz")
+        grid = BinGrid()
+        xp = _ptr(obs_xyz) if nobs else None
+        self._check(self.lib.cwbl_bin_index(nobs, xp, hclr, vclr, int(div), C.byref(grid), 0,
+                                            None, None, memory))
+        if grid_only:
+            return grid, None, None
+        ncell = grid.nbx * grid.nby * grid.nbz
+        if memory == MEM_HOST:
+            start, order = np.empty(ncell + 1, np.int32), np.empty(nobs, np.int32)
+        else:
+            import torch
+            start = torch.empty(ncell + 1, dtype=torch.int32, device=obs_xyz.device)
+            order = torch.empty(nobs, dtype=torch.int32, device=obs_xyz.device)
+        self._check(self.lib.cwbl_bin_index(nobs, xp, hclr, vclr, int(div), C.byref(grid),
+                                            ncell + 1, _ptr(start), _ptr(order) if nobs else None,
+                                            memory))
+        return grid, start, order
+
+    def prep_info(self):
+        """cwbl_prep_info: the search-index split of the last analyze_var (PrepInfo)."""
+        info = PrepInfo()
+        self._check(self.lib.cwbl_prep_info(C.byref(info)))
+        return info
 
     # ---- member <-> column transposes (device pointers; see cwbl/transpose.py) ----------
     def pack_columns(self, global_field, nx, ny, nz, px, py, send):

@@ -68,6 +68,19 @@ module letkf_core_gpu
         real(c_double)       :: ms_total, ms_prep, ms_search, ms_solve, ms_copy
     end type cwbl_stats
 
+    ! cwbl_set_option: the search index mode (0 host build, 1 device bins + tree on demand)
+    integer(c_int), parameter, public :: CWBL_OPT_INDEX = 13
+
+    type, bind(C), public :: cwbl_bin_grid         ! cwbl_bin_index
+        real(c_float)  :: x0, y0, z0, binv
+        integer(c_int) :: nbx, nby, nbz, div
+    end type cwbl_bin_grid
+
+    type, bind(C), public :: cwbl_prep_info_t      ! cwbl_prep_info
+        integer(c_int) :: trees_built, bins_built, bins_on_device, flagged_batches
+        real(c_double) :: ms_tree, ms_bins, ms_columns, ms_tree_wait
+    end type cwbl_prep_info_t
+
     ! projection_nml (module_config.f90:70-75), include/cwb_letkf_ingest.h
     type, bind(C), public :: cwbl_projection
         real(c_float) :: sta_lon, cen_lat, truelat1, truelat2
@@ -77,6 +90,7 @@ module letkf_core_gpu
               cwbl_pack_columns, cwbl_unpack_columns, cwbl_pack_members, cwbl_unpack_members, &
               cwbl_vcoord_mean, &
               cwbl_member_sum, cwbl_scale, cwbl_set_stream, cwbl_set_option, &
+              cwbl_bin_index, cwbl_prep_info, &
               cwbl_finalize, cwbl_abi_version, cwbl_error, cwbl_check
     ! host obs ingest (include/cwb_letkf_ingest.h); file names and varname are passed as
     ! trim(name)//c_null_char
@@ -258,6 +272,23 @@ module letkf_core_gpu
             integer(c_int),       value :: option
             integer(c_long_long), value :: val
         end function cwbl_set_option
+
+        ! the device-built search bins of one obs type (start = c_null_ptr: the grid only)
+        integer(c_int) function cwbl_bin_index(nobs, obs_xyz, hclr, vclr, div, grid, start_cap, &
+                start, order, memory) bind(C, name='cwbl_bin_index')
+            import :: c_int, c_long_long, c_float, c_ptr, cwbl_bin_grid
+            integer(c_int),       value       :: nobs, div, memory
+            real(c_float),        value       :: hclr, vclr
+            type(c_ptr),          value       :: obs_xyz, start, order
+            type(cwbl_bin_grid),  intent(out) :: grid
+            integer(c_long_long), value       :: start_cap
+        end function cwbl_bin_index
+
+        ! the search-index split of the last cwbl_analyze_var
+        integer(c_int) function cwbl_prep_info(info) bind(C, name='cwbl_prep_info')
+            import :: c_int, cwbl_prep_info_t
+            type(cwbl_prep_info_t), intent(out) :: info
+        end function cwbl_prep_info
 
         integer(c_int) function cwbl_finalize() bind(C, name='cwbl_finalize')
             import :: c_int

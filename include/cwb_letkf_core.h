@@ -309,10 +309,52 @@ enum {
                                 * divisor are rebuilt) */
   CWBL_OPT_LEAD_DIV = 10,      /* first search batch = points / value (0 = off, default) */
   CWBL_OPT_MAX_BATCH = 11,     /* points per search batch, >= 256 (0 = automatic, default) */
-  CWBL_OPT_INFO_WINDOW = 12    /* points per reduction of the per-point solve info, >= 256
+  CWBL_OPT_INFO_WINDOW = 12,   /* points per reduction of the per-point solve info, >= 256
                                 * (0 = 2^25, default; smaller values exercise the rollover) */
+  CWBL_OPT_INDEX = 13          /* search index of the next cwbl_analyze_var: 0 k-d tree and bins
+                                * built on the host (default); 1 bins built on the device from
+                                * the obs coordinates, columns in obs order, the k-d tree built
+                                * by a host thread and used only where a list truncates (or
+                                * for every point with CWBL_OPT_SEARCH = 1).  Cached indexes
+                                * of the two modes are kept apart */
 };
 int         cwbl_set_option(int option, long long value);
+
+/* ---- search index (no reference counterpart: the reference walks its k-d tree) ------------
+ * The uniform bins of the analysis search for one obs type, built on the device: the
+ * counterpart of cwbl_search for the binned path.  obs_xyz(3,nobs) metres, hclr/vclr km
+ * (vclr <= 0: 2-D); div: cell side = search radius / div, 1..8 (0 = by obs density).  The
+ * grid is that of the analysis: origin at the minima of the finite normalised coordinates,
+ * cell (ix, iy, iz) = floor((x - x0) * binv) per dimension clamped to the grid (fp32), cells
+ * x-fastest, a point with a non-finite coordinate in cell 0.  order(nobs): the obs indices
+ * (0-based) sorted by cell, ascending within a cell; start(ncell + 1): cell c holds
+ * order[start[c] .. start[c + 1]).  With start == NULL only `grid` is filled, so the caller
+ * can size start (nbx*nby*nbz + 1 entries, start_cap says how many it holds) and order.
+ * `memory` tells where obs_xyz, start and order live. */
+typedef struct cwbl_bin_grid {
+  float x0, y0, z0, binv;   /* origin and 1 / cell side, normalised units */
+  int   nbx, nby, nbz;      /* cells per dimension (nbz = 1 in 2-D); at most 2^22 in all */
+  int   div;                /* the divisor used (the cap may have grown the cells beyond it) */
+} cwbl_bin_grid;
+int         cwbl_bin_index(int nobs, const float *obs_xyz, float hclr, float vclr, int div,
+                           cwbl_bin_grid *grid, long long start_cap, int *start, int *order,
+                           int memory);
+
+/* What the last cwbl_analyze_var spent on its search index (the split of cwbl_stats.ms_prep),
+ * in both index modes. */
+typedef struct cwbl_prep_info_t {
+  int    trees_built;      /* host k-d tree builds started by the call */
+  int    bins_built;       /* bin sets built by the call (0: all came from the cache) */
+  int    bins_on_device;   /* of those, built on the device */
+  int    flagged_batches;  /* CWBL_OPT_INDEX = 1: search batches with a point whose list
+                            * passes max_lz_pts (mode 0 never reads the count back) */
+  double ms_tree;          /* host time of the k-d builds the call used (CWBL_OPT_INDEX = 1:
+                            * the worker's own time, counted when the tree is first needed) */
+  double ms_bins;          /* host build_bins, or the device build on its stream (HIP events) */
+  double ms_columns;       /* obs_prep_kernel (HIP events) */
+  double ms_tree_wait;     /* CWBL_OPT_INDEX = 1: time the call waited for a tree worker */
+} cwbl_prep_info_t;
+int         cwbl_prep_info(cwbl_prep_info_t *out);
 
 int         cwbl_finalize(void);
 const char *cwbl_last_error(void);
