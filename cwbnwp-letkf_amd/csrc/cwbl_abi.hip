@@ -228,6 +228,46 @@ enum KernelId {
 };
 struct KTime { long long launches = 0, points = 0; double ms = 0.0; };
 
+// Record reuse (CWBL_OPT_RECORD_REUSE): the k = 17..40 record path keeps what one call's
+// assemblies wrote, keyed by everything the record depends on.  The record holds A = inflat I
+// + Yb Yb^T and b1 = Yb d: functions of the obs set, the types' parameters, the weight
+// function, multi_infl and the point coordinates, not of the analysed variable (var enters in
+// solve_tq40_kernel only).  A later call with an equal key and bit-equal coordinates launches
+// the solves on the kept records and nothing before them.
+struct RecordKey {
+  unsigned long long gen;  // State::gen: obs set, cwbl_init constants, options
+  float multi_infl;        // inflat is on the record's diagonal
+  int dims[7];             // nx, ny, nz, alt_nx, alt_ny, ix_lim, iy_lim
+  cwbl_type_params gts[CWBL_NUM_GTS_TYPES], radar[CWBL_NUM_RADAR_TYPES];
+};
+struct RecordCache {
+  bool valid = false;  // a fill completed: everything below describes it
+  RecordKey key{};
+  // Batch b < off.size() of `plan` (the leading batches that fit the budget) keeps its nb
+  // records and the spare one that solve_tq40_kernel's lanes past a launch read, from word
+  // off[b] of `rec`; sub-batch s0 of it starts s0 records on, its spare being the next
+  // sub-batch's first record.  info: (p, level) of the pts cached points as the fill left
+  // them; a hit restores p.  sx, sy, salt: the coordinates the records were assembled from.
+  DevBuf rec, info, sx, sy, salt, flag;
+  PinBuf hflag;
+  std::vector<std::pair<long long, int>> plan;
+  std::vector<size_t> off;
+  long long pts = 0;
+  size_t nxy = 0, nalt = 0;
+  // what a call that skips plan_trees and the searches still reports
+  int nt = 0, list_cap = 0;
+  long long lz_truncated = 0, q1_undefined = 0;
+  size_t bytes() const { return rec.n + info.n + sx.n + sy.n + salt.n + flag.n; }
+  void release() {
+    valid = false;
+    for (DevBuf *b : {&rec, &info, &sx, &sy, &salt, &flag}) b->release();
+    hflag.release();
+    plan.clear();
+    off.clear();
+    pts = 0;
+  }
+};
+
 struct State {
   bool inited = false;
   int k = 0, kp = 0, device = 0, wf = 0, q1_mode = 0;
@@ -286,6 +326,9 @@ struct State {
   struct KPend { int id; hipEvent_t e0, e1; long long pts; };
   std::vector<KPend> kpend;
   size_t handoff_budget = 0;                          // bytes for the k > 64 hand-off records
+  unsigned long long gen = 0;     // bumped by cwbl_init, cwbl_set_obs and cwbl_set_option
+  size_t reuse_budget = 0;        // CWBL_OPT_RECORD_REUSE in bytes (0: no reuse)
+  RecordCache cache;
   // pageable host slabs: each batch's var columns go through page-locked bounce slots (two
   // in, two out), filled and drained by a few host threads while the GPU runs other batches
   static constexpr int kSlots = 3;
@@ -525,6 +568,8 @@ int bin_div_for(const HostTree &t, int dim) {
   }
   return bin_div_density(n, lo, hi, dim);
 }
+
+cwbl_reuse_info_t R;  // cwbl_reuse_info: what the current cwbl_analyze_var reused
 
 // ---- cwbl_prep_info: what the current cwbl_analyze_var spends on its search index -----------
 cwbl_prep_info_t P;
@@ -861,6 +906,7 @@ void release_all() {
                     &S.ix_part})
     b->release();
   S.ix_pin.release();
+  S.cache.release();
   for (hipEvent_t e : S.pevents) (void)hipEventDestroy(e);
   S.pevents.clear();
   g_pspans.clear();
@@ -958,7 +1004,109 @@ struct VarCall {
   int ev = 4, cev = 0;
   std::vector<std::pair<int, int>> search_ev, solve_ev;
   std::vector<int> done_ev, h2d_done, d2h_done;
+  // record reuse: 1 = this call fills the cache, 2 = it solves from it (the leading ncached
+  // batches; full_hit: every batch, so no tree, column table or search is needed at all)
+  int reuse = 0;
+  long long ncached = 0;
+  bool full_hit = false;
 };
+
+bool record_path() { return S.tq4 && S.kp == kTq4KP && !S.jacobi; }
+
+void make_record_key(RecordKey &key, const cwbl_var_params *vp, const cwbl_slab *sl) {
+  std::memset(&key, 0, sizeof key);
+  key.gen = S.gen;
+  key.multi_infl = vp->multi_infl;
+  const int dims[7] = {sl->nx, sl->ny, sl->nz, sl->alt_nx, sl->alt_ny, sl->ix_lim, sl->iy_lim};
+  std::memcpy(key.dims, dims, sizeof dims);
+  std::memcpy(key.gts, vp->gts, sizeof key.gts);
+  std::memcpy(key.radar, vp->radar, sizeof key.radar);
+}
+
+// The hit test behind an equal key: the slab's coordinates (staged copies for a host slab)
+// against the fill's snapshot, exactly.  A caller may have rewritten x, y or alt in place
+// behind unchanged pointers.  One synchronisation of S.stream.
+int coords_match(VarCall &v, bool &same) {
+  RecordCache &C = S.cache;
+  const auto t0 = std::chrono::steady_clock::now();
+  int *flag = C.flag.as<int>();
+  HIPCHK(hipMemsetAsync(flag, 0, sizeof(int), S.stream));
+  HIPCHK(launch_coord_snapshot(S.stream, false, v.sd.x, C.sx.as<float>(), (long long)C.nxy, flag));
+  HIPCHK(launch_coord_snapshot(S.stream, false, v.sd.y, C.sy.as<float>(), (long long)C.nxy, flag));
+  HIPCHK(launch_coord_snapshot(S.stream, false, v.sd.alt, C.salt.as<float>(), (long long)C.nalt,
+                               flag));
+  HIPCHK(hipMemcpyAsync(C.hflag.p, flag, sizeof(int), hipMemcpyDeviceToHost, S.stream));
+  HIPCHK(hipStreamSynchronize(S.stream));
+  same = *C.hflag.as<int>() == 0;
+  R.ms_compare = ms_since(t0);
+  return CWBL_OK;
+}
+
+// A call whose key or coordinates differ from the cache's: plans which leading batches'
+// records fit the budget, allocates what they need (kept from an earlier fill when it is
+// large enough) and takes the coordinate snapshot.  The batches then assemble into their own
+// regions instead of S.wsa.  A failed allocation is no error: the call runs without reuse.
+int begin_fill(VarCall &v, const RecordKey &key) {
+  RecordCache &C = S.cache;
+  C.valid = false;
+  C.key = key;
+  C.plan = v.plan;
+  C.off.clear();
+  C.pts = 0;
+  size_t words = 0;
+  for (const auto &b : v.plan) {
+    const size_t need = ((size_t)b.second + 1) * AsmRecord<kTq4KP>::WORDS;
+    if ((words + need) * sizeof(double) > S.reuse_budget) break;
+    C.off.push_back(words);
+    words += need;
+    C.pts += b.second;
+  }
+  if (C.off.empty()) return CWBL_OK;
+  const cwbl_slab *sl = v.sl;
+  C.nxy = (size_t)sl->nx * sl->ny;
+  C.nalt = (size_t)sl->alt_nx * sl->alt_ny * sl->nz;
+  // Grow-only, with 1/16 of headroom within the budget: the slabs of one cycle differ by a
+  // staggered row, column or level (2 % at 300 x 300 x 50), and replacing the buffer is dear
+  // (bench.py's cycle leg once lost 1.6 s to the regrow of 31 GB for a 51-level slab)
+  const size_t need = words * sizeof(double);
+  bool ok = need <= C.rec.n ||
+            C.rec.ensure(std::min(S.reuse_budget, need + need / 16)) == hipSuccess;
+  ok = ok && C.info.ensure((size_t)C.pts * sizeof(int2)) == hipSuccess;
+  ok = ok && C.sx.ensure(C.nxy * 4) == hipSuccess && C.sy.ensure(C.nxy * 4) == hipSuccess;
+  ok = ok && C.salt.ensure(C.nalt * 4) == hipSuccess && C.flag.ensure(sizeof(int)) == hipSuccess;
+  ok = ok && C.hflag.ensure(64) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    C.release();
+    return CWBL_OK;
+  }
+  HIPCHK(launch_coord_snapshot(S.stream, true, v.sd.x, C.sx.as<float>(), (long long)C.nxy, nullptr));
+  HIPCHK(launch_coord_snapshot(S.stream, true, v.sd.y, C.sy.as<float>(), (long long)C.nxy, nullptr));
+  HIPCHK(launch_coord_snapshot(S.stream, true, v.sd.alt, C.salt.as<float>(), (long long)C.nalt,
+                               nullptr));
+  v.reuse = 1;
+  v.ncached = (long long)C.off.size();
+  return CWBL_OK;
+}
+
+// The info window that opens at point g on a hit: the cached points' accepted counts, which
+// solve_tq40_kernel reads where the assembly would have left them.
+int restore_info(VarCall &v, long long g) {
+  const long long n = std::min<long long>(v.info_cap, S.cache.pts - g);
+  if (v.reuse != 2 || n <= 0) return CWBL_OK;
+  HIPCHK(hipMemcpyAsync(S.info.p, S.cache.info.as<int2>() + g, (size_t)n * sizeof(int2),
+                        hipMemcpyDeviceToDevice, S.stream));
+  return CWBL_OK;
+}
+
+// The info window [v.win0, end) as a fill's solves left it (p is what the assembly wrote).
+int keep_info(VarCall &v, long long end) {
+  const long long n = std::min<long long>(end, S.cache.pts) - v.win0;
+  if (v.reuse != 1 || n <= 0) return CWBL_OK;
+  HIPCHK(hipMemcpyAsync(S.cache.info.as<int2>() + v.win0, S.info.p, (size_t)n * sizeof(int2),
+                        hipMemcpyDeviceToDevice, S.stream));
+  return CWBL_OK;
+}
 
 // build_tree of both families and the upload of their descriptors (nt = 0: nothing to do)
 // Index mode 1, when a search first needs the trees: join the workers of the types that have
@@ -1299,9 +1447,11 @@ long long sub_batch(int nb, long long cap) {
 //   otherwise    one wavefront per point: solve_tq_kernel; CWBL_OPT_SOLVER = 1: the Jacobi
 //                eigensolver kernel (k <= 64)
 // b2 / dn: the events around the batch's solve (the record path times its kernel pair
-// between them).
+// between them).  crec (record path): the batch's region of the record cache, which a fill
+// assembles into and a hit (no lists, no assembly) solves from; null: S.wsa.
 int solve_batch_path(VarCall &v, long long g0, int nb, const int *ncnt, const int *nidx,
-                     int2 *infob, hipEvent_t b2, hipEvent_t dn) {
+                     int2 *infob, hipEvent_t b2, hipEvent_t dn, double *crec = nullptr,
+                     bool hit = false) {
   const TreeDesc *dtrees = S.tdesc.as<TreeDesc>();
   const SolveConsts &c = v.c;
   const SlabDev &sd = v.sd;
@@ -1314,8 +1464,15 @@ int solve_batch_path(VarCall &v, long long g0, int nb, const int *ncnt, const in
     const long long cap = std::min<long long>(S.tq4_sub > 0 ? S.tq4_sub : nb, 1 << 19);
     const long long Bs = std::min<long long>(sub_batch(nb, cap), 1 << 19);
     // (+1: the spare record of solve_tq40_kernel's lanes past the sub-batch)
-    HIPCHK(S.wsa.ensure((size_t)(Bs + 1) * 8 * AsmRecord<kTq4KP>::WORDS));
-    double *rec = S.wsa.as<double>();
+    if (!crec) HIPCHK(S.wsa.ensure((size_t)(Bs + 1) * 8 * AsmRecord<kTq4KP>::WORDS));
+    double *rec = crec ? crec : S.wsa.as<double>();
+    // a cached batch keeps every sub-batch's records, S.wsa only the current one's
+    const size_t rstep = crec ? AsmRecord<kTq4KP>::WORDS : 0;
+    if (Bs >= nb && hit) {
+      if (S.ktiming) S.kpend.push_back({KT_SOLVE_TQ40, b2, dn, nb});
+      HIPCHK(launch_solve_tq40(S.stream, S.kp, c, sd, g0, nb, rec, infob));
+      return CWBL_OK;
+    }
     if (Bs >= nb) {  // the whole batch: timed between b2 and dn (recorded anyway)
       auto asm_ = [&]() {
         return launch_assemble_record(S.stream, S.kp, dtrees, c, sd, g0, nb, ncnt, nidx, infob,
@@ -1327,12 +1484,15 @@ int solve_batch_path(VarCall &v, long long g0, int nb, const int *ncnt, const in
     }
     for (long long s0 = 0; s0 < nb; s0 += Bs) {
       const int ns = (int)std::min<long long>(Bs, nb - s0);
+      double *const srec = rec + (size_t)s0 * rstep;
+      if (!hit) {
+        HIPCHK(kt_begin(S.stream, &kt));
+        HIPCHK(launch_assemble_record(S.stream, S.kp, dtrees, c, sd, g0 + s0, ns,
+                                      ncnt + s0 * nt, nidx + s0 * list_cap, infob + s0, srec));
+        HIPCHK(kt_end(S.stream, kt, KT_ASSEMBLE_RECORD, ns));
+      }
       HIPCHK(kt_begin(S.stream, &kt));
-      HIPCHK(launch_assemble_record(S.stream, S.kp, dtrees, c, sd, g0 + s0, ns, ncnt + s0 * nt,
-                                    nidx + s0 * list_cap, infob + s0, rec));
-      HIPCHK(kt_end(S.stream, kt, KT_ASSEMBLE_RECORD, ns));
-      HIPCHK(kt_begin(S.stream, &kt));
-      HIPCHK(launch_solve_tq40(S.stream, S.kp, c, sd, g0 + s0, ns, rec, infob + s0));
+      HIPCHK(launch_solve_tq40(S.stream, S.kp, c, sd, g0 + s0, ns, srec, infob + s0));
       HIPCHK(kt_end(S.stream, kt, KT_SOLVE_TQ40, ns));
     }
     return CWBL_OK;
@@ -1382,8 +1542,10 @@ int solve_batch_path(VarCall &v, long long g0, int nb, const int *ncnt, const in
 // synchronisation, and the statistics.
 int finish_call(VarCall &v, cwbl_stats &st) {
   DevStats *dst = S.stats.as<DevStats>();
-  if (v.npts > v.win0)
+  if (v.npts > v.win0) {
     HIPCHK(launch_reduce_info(S.stream, S.info.as<int2>(), (int)(v.npts - v.win0), dst));
+    if (int rc = keep_info(v, v.npts)) return rc;
+  }
   int ev = v.ev;
   if (v.vp->tune_q) {
     hipEvent_t a, b;
@@ -1422,7 +1584,9 @@ int finish_call(VarCall &v, cwbl_stats &st) {
 
   st.solved = (long long)ds.solved;
   st.nobs_sum = (long long)ds.nobs_sum;
-  st.lz_truncated = (long long)ds.lz_truncated;
+  // (a hit ran none, or only the uncached batches', of the searches that count this: the
+  // inputs being equal, the fill's total holds)
+  st.lz_truncated = v.reuse == 2 ? S.cache.lz_truncated : (long long)ds.lz_truncated;
   st.nonconverged = (long long)ds.nonconverged;
   st.sweeps_sum = (long long)ds.sweeps_sum;
   st.max_p = (int)ds.max_p;
@@ -1483,13 +1647,16 @@ int cwbl_init(const cwbl_init_params *p) {
   S.norain = p->norain_value;
   S.q1_mode = p->q1_mode;
   S.ws_bytes = p->workspace_bytes ? p->workspace_bytes : (size_t(2) << 30);
+  size_t fr = 0, tot = 0;
+  HIPCHK(hipMemGetInfo(&fr, &tot));
   if (p->workspace_bytes) {
     S.handoff_budget = p->workspace_bytes;
   } else {  // 13 GB (98 304 points at k = 128), at most 40% of what is free now
-    size_t fr = 0, tot = 0;
-    HIPCHK(hipMemGetInfo(&fr, &tot));
     S.handoff_budget = std::min<size_t>((size_t)13 << 30, fr / 10 * 4);
   }
+  // records kept for reuse (CWBL_OPT_RECORD_REUSE): 40 GiB holds a 300 x 300 x 50 slab's 31 GB
+  S.reuse_budget = std::min<size_t>((size_t)40 << 30, fr / 10 * 4);
+  ++S.gen;
   HIPCHK(hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking));
   HIPCHK(hipStreamCreateWithFlags(&S.sstream, hipStreamNonBlocking));
   HIPCHK(hipStreamCreateWithFlags(&S.h2d, hipStreamNonBlocking));
@@ -1533,6 +1700,7 @@ int cwbl_init(const cwbl_init_params *p) {
 int cwbl_set_option(int option, long long value) {
   if (!S.inited) return fail(CWBL_ERR_STATE, "cwbl_set_option before cwbl_init");
   auto range = [&](long long lo, long long hi) { return value >= lo && value <= hi; };
+  ++S.gen;  // options change the neighbour order and the batch plan: kept records are void
   switch (option) {
     case CWBL_OPT_SOLVER:
       if (!range(0, 1)) break;
@@ -1587,6 +1755,11 @@ int cwbl_set_option(int option, long long value) {
       if (!range(0, 1)) break;
       S.index_mode = (int)value;
       return CWBL_OK;
+    case CWBL_OPT_RECORD_REUSE:
+      if (!range(0, 1LL << 24)) break;
+      S.reuse_budget = (size_t)value << 20;
+      S.cache.release();  // the next fill allocates within the new budget
+      return CWBL_OK;
     default:
       return fail(CWBL_ERR_ARG, "cwbl_set_option: unknown option %d", option);
   }
@@ -1628,6 +1801,13 @@ int cwbl_kernel_times(cwbl_kernel_time *out, int cap, int *n) {
   return CWBL_OK;
 }
 
+int cwbl_reuse_info(cwbl_reuse_info_t *out) {
+  if (int rc = require_device()) return rc;
+  if (!out) return fail(CWBL_ERR_ARG, "cwbl_reuse_info: null argument");
+  *out = R;
+  return CWBL_OK;
+}
+
 int cwbl_finalize(void) {
   if (S.inited) {
     (void)hipStreamSynchronize(S.stream);
@@ -1642,6 +1822,7 @@ int cwbl_set_obs(const cwbl_obs_set *o) {
   if (o->n_gts < 0 || o->n_radar < 0 || (o->n_gts && !o->gts) || (o->n_radar && !o->radar))
     return fail(CWBL_ERR_ARG, "bad obs set counts/pointers");
   release_obs();
+  ++S.gen;  // (the record cache keeps its allocation: only its contents are void)
   const int mem = o->memory;
   if (mem == CWBL_MEM_DEVICE) HIPCHK(order_after_caller());
   const size_t k = (size_t)S.k;
@@ -1748,7 +1929,34 @@ int cwbl_analyze_var(const cwbl_var_params *vp, const cwbl_slab *sl, cwbl_stats 
   hipEvent_t e0, e1, e2, e_ready;
   HIPCHK(event(0, &e0));
   HIPCHK(hipEventRecord(e0, S.stream));
-  if (int rc = plan_trees(v)) return rc;
+  // Record reuse: an equal key makes the call a candidate; the coordinates decide.  (A
+  // candidate stages its slab first, so its ms_prep holds the staging and the compare.)
+  RecordCache &C = S.cache;
+  std::memset(&R, 0, sizeof R);
+  const bool reuse_on = record_path() && S.reuse_budget > 0 && npts > 0;
+  RecordKey key;
+  bool staged = false;
+  if (reuse_on) {
+    make_record_key(key, vp, sl);
+    if (C.valid && std::memcmp(&key, &C.key, sizeof key) == 0) {
+      if (int rc = stage_slab(v)) return rc;
+      staged = true;
+      bool same = false;
+      if (int rc = coords_match(v, same)) return rc;
+      if (same) {
+        v.reuse = 2;
+        v.ncached = (long long)C.off.size();
+        v.full_hit = C.off.size() == C.plan.size();
+      }
+    }
+    if (v.reuse != 2) C.valid = false;
+  }
+  if (v.full_hit) {
+    v.nt = C.nt;
+    v.list_cap = C.list_cap;
+  } else if (int rc = plan_trees(v)) {
+    return rc;
+  }
   st.ntrees = v.nt;
   if (v.nt == 0 || npts == 0) {  // `if(all(.not. succeed)) cycle` (:66)
     HIPCHK(hipStreamSynchronize(S.stream));
@@ -1756,14 +1964,21 @@ int cwbl_analyze_var(const cwbl_var_params *vp, const cwbl_slab *sl, cwbl_stats 
     return finish();
   }
   for (const TreeDesc &d : v.descs) st.q1_undefined += d.q1_undef ? npts : 0;
+  if (v.full_hit) st.q1_undefined = C.q1_undefined;
   HIPCHK(event(1, &e1));
   HIPCHK(hipEventRecord(e1, S.stream));
   HIPCHK(event(2, &e2));
-  if (int rc = stage_slab(v)) return rc;
+  if (!staged)
+    if (int rc = stage_slab(v)) return rc;
   HIPCHK(hipEventRecord(e2, S.stream));
   plan_batches(v);
+  if (v.reuse == 2 && v.plan != C.plan)
+    return fail(CWBL_ERR_STATE, "record reuse: the batch plan changed under an equal key");
   if (int rc = stage_bounce(v)) return rc;
   if (int rc = alloc_call_buffers(v)) return rc;
+  if (reuse_on && v.reuse != 2)
+    if (int rc = begin_fill(v, key)) return rc;
+  if (int rc = restore_info(v, 0)) return rc;
   HIPCHK(event(3, &e_ready));  // inputs staged and the counters cleared
   HIPCHK(hipEventRecord(e_ready, S.stream));
   HIPCHK(hipStreamWaitEvent(S.sstream, e_ready, 0));
@@ -1778,7 +1993,9 @@ int cwbl_analyze_var(const cwbl_var_params *vp, const cwbl_slab *sl, cwbl_stats 
     if (g0 + nb - v.win0 > v.info_cap) {  // close the info window; S.stream orders the reuse
       HIPCHK(launch_reduce_info(S.stream, S.info.as<int2>(), (int)(g0 - v.win0),
                                 S.stats.as<DevStats>()));
+      if (int rc = keep_info(v, g0)) return rc;
       v.win0 = g0;
+      if (int rc = restore_info(v, g0)) return rc;
     }
     int2 *const infob = S.info.as<int2>() + (g0 - v.win0);  // this batch's info
     int *ncnt = (bi & 1) ? S.nbr_cnt2.as<int>() : S.nbr_cnt.as<int>();
@@ -1789,12 +2006,17 @@ int cwbl_analyze_var(const cwbl_var_params *vp, const cwbl_slab *sl, cwbl_stats 
     HIPCHK(event(ev + 1, &b));
     HIPCHK(event(ev + 2, &b2));
     HIPCHK(event(ev + 3, &dn));
-    if (int rc = search_batch(v, bi, ncnt, nidx, a, b)) return rc;
-    HIPCHK(hipStreamWaitEvent(S.stream, b, 0));
+    // a cached batch: its region of the record cache; on a hit neither lists nor assembly
+    double *const crec = bi < v.ncached ? C.rec.as<double>() + C.off[bi] : nullptr;
+    const bool hit = crec && v.reuse == 2;
+    if (!hit) {
+      if (int rc = search_batch(v, bi, ncnt, nidx, a, b)) return rc;
+      HIPCHK(hipStreamWaitEvent(S.stream, b, 0));
+    }
     if (v.piped)
       if (int rc = upload_batch_var(v, bi)) return rc;
     HIPCHK(hipEventRecord(b2, S.stream));
-    if (int rc = solve_batch_path(v, g0, nb, ncnt, nidx, infob, b2, dn)) return rc;
+    if (int rc = solve_batch_path(v, g0, nb, ncnt, nidx, infob, b2, dn, crec, hit)) return rc;
     HIPCHK(hipEventRecord(dn, S.stream));  // this batch's lists are free again
     if (v.piped_back)
       if (int rc = return_batch_var(v, bi, dn)) return rc;
@@ -1804,12 +2026,22 @@ int cwbl_analyze_var(const cwbl_var_params *vp, const cwbl_slab *sl, cwbl_stats 
       if (v.piped_back && bi >= State::kSlots - 1)
         if (int rc = bounce_drain(v, bi - (State::kSlots - 1))) return rc;
     }
-    v.search_ev.push_back({ev, ev + 1});
+    if (!hit) v.search_ev.push_back({ev, ev + 1});
     v.solve_ev.push_back({ev + 2, ev + 3});
     v.done_ev.push_back(ev + 3);
     v.ev += 4;
   }
   if (int rc = finish_call(v, st)) return rc;
+  if (v.reuse == 1) {  // the fill is complete: the next call may solve from it
+    C.nt = v.nt;
+    C.list_cap = v.list_cap;
+    C.lz_truncated = st.lz_truncated;
+    C.q1_undefined = st.q1_undefined;
+    C.valid = true;
+  }
+  R.batches_reused = v.reuse == 2 ? v.ncached : 0;
+  R.batches_assembled = nbat - R.batches_reused;
+  R.bytes_held = (long long)C.bytes();
   return finish();
 }
 

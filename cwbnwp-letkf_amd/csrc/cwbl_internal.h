@@ -326,6 +326,11 @@ hipError_t launch_search_single(hipStream_t s, const TreeDesc *tree, int depth, 
 
 hipError_t launch_reduce_info(hipStream_t s, const int2 *info, int n, DevStats *stats);
 
+// Record reuse: n coordinates `cur` against their snapshot `snap`, bit for bit (*flag, zeroed
+// by the caller, becomes 1 on any mismatch); store: snap = cur instead (flag unused).
+hipError_t launch_coord_snapshot(hipStream_t s, bool store, const float *cur, float *snap,
+                                 long long n, int *flag);
+
 constexpr int kSearchStackDepth = 40;  // max k-d tree depth the search kernel supports
 
 // Neighbour lists of the analysis path are interleaved by groups of kListLanes points and

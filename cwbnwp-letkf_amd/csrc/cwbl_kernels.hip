@@ -993,4 +993,33 @@ hipError_t launch_reduce_info(hipStream_t s, const int2 *info, int n, DevStats *
   return hipGetLastError();
 }
 
+// Record reuse (cwbl_abi.hip, RecordCache): the slab's coordinates against their snapshot, as
+// bit patterns (a NaN equals itself, -0 differs from +0).  STORE: takes the snapshot instead.
+// A mismatch raises *flag; every writer stores the same 1, so the race is benign.
+template <bool STORE>
+__global__ void __launch_bounds__(256)
+coord_snapshot_kernel(const unsigned *__restrict__ cur, unsigned *__restrict__ snap, long long n,
+                      int *__restrict__ flag) {
+  bool diff = false;
+  for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n;
+       e += (long long)gridDim.x * 256) {
+    if constexpr (STORE) snap[e] = cur[e];
+    else diff |= cur[e] != snap[e];
+  }
+  if (diff) *flag = 1;
+}
+
+hipError_t launch_coord_snapshot(hipStream_t s, bool store, const float *cur, float *snap,
+                                 long long n, int *flag) {
+  if (n <= 0) return hipSuccess;
+  const dim3 grid((unsigned)std::min<long long>((n + 255) / 256, 8192));
+  const unsigned *c = reinterpret_cast<const unsigned *>(cur);
+  unsigned *p = reinterpret_cast<unsigned *>(snap);
+  if (store)
+    hipLaunchKernelGGL(coord_snapshot_kernel<true>, grid, dim3(256), 0, s, c, p, n, flag);
+  else
+    hipLaunchKernelGGL(coord_snapshot_kernel<false>, grid, dim3(256), 0, s, c, p, n, flag);
+  return hipGetLastError();
+}
+
 }  // namespace cwbl

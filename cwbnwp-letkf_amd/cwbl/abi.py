@@ -28,12 +28,13 @@ GTS_NVAR = {GTS_SOUND: 4, GTS_SYNOP: 5, GTS_GPSPW: 1, GTS_METAR: 5, GTS_SHIPS: 5
 #: cwbl_set_option options (include/cwb_letkf_core.h)
 OPT_SOLVER, OPT_SPLIT40, OPT_SPLIT40_BATCH, OPT_SEARCH = 1, 2, 3, 5
 OPT_BIG_PATH, OPT_BIG_BATCH, OPT_PAGEABLE, OPT_BIN_DIV, OPT_LEAD_DIV, OPT_MAX_BATCH = 6, 7, 8, 9, 10, 11
-OPT_INFO_WINDOW, OPT_INDEX = 12, 13
+OPT_INFO_WINDOW, OPT_INDEX, OPT_RECORD_REUSE = 12, 13, 14
 OPTIONS = {"solver": OPT_SOLVER, "split40": OPT_SPLIT40, "split40_batch": OPT_SPLIT40_BATCH,
            "search": OPT_SEARCH,
            "big_path": OPT_BIG_PATH, "big_batch": OPT_BIG_BATCH, "pageable": OPT_PAGEABLE,
            "bin_div": OPT_BIN_DIV, "lead_div": OPT_LEAD_DIV, "max_batch": OPT_MAX_BATCH,
-           "info_window": OPT_INFO_WINDOW, "index": OPT_INDEX}
+           "info_window": OPT_INFO_WINDOW, "index": OPT_INDEX,
+           "record_reuse": OPT_RECORD_REUSE}
 
 ERRORS = {1: "CWBL_ERR_ARG", 2: "CWBL_ERR_STATE", 3: "CWBL_ERR_NO_DEVICE", 4: "CWBL_ERR_HIP",
           5: "CWBL_ERR_UNSUPPORTED", 6: "CWBL_ERR_OOM"}
@@ -112,11 +113,19 @@ class PrepInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class ReuseInfo(C.Structure):
+    _fields_ = [("batches_reused", C.c_longlong), ("batches_assembled", C.c_longlong),
+                ("bytes_held", C.c_longlong), ("ms_compare", C.c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 #: exported symbols of the product library (include/cwb_letkf_core.h)
 EXPORTS = ["cwbl_init", "cwbl_set_stream", "cwbl_set_obs", "cwbl_analyze_var", "cwbl_solve_batch", "cwbl_search",
            "cwbl_pack_columns", "cwbl_unpack_columns", "cwbl_pack_members",
            "cwbl_unpack_members", "cwbl_vcoord_mean", "cwbl_member_sum", "cwbl_scale", "cwbl_set_kernel_timing", "cwbl_kernel_times",
-           "cwbl_set_option", "cwbl_bin_index", "cwbl_prep_info",
+           "cwbl_set_option", "cwbl_bin_index", "cwbl_prep_info", "cwbl_reuse_info",
            "cwbl_finalize", "cwbl_last_error", "cwbl_abi_version"]
 
 
@@ -299,6 +308,7 @@ def load_library(path=None):
     lib.cwbl_bin_index.argtypes = [C.c_int, vp, C.c_float, C.c_float, C.c_int, C.POINTER(BinGrid),
                                    C.c_longlong, vp, vp, C.c_int]
     lib.cwbl_prep_info.argtypes = [C.POINTER(PrepInfo)]
+    lib.cwbl_reuse_info.argtypes = [C.POINTER(ReuseInfo)]
     lib.cwbl_finalize.argtypes = []
     lib.cwbl_last_error.restype = cp
     lib.cwbl_abi_version.restype = C.c_int
@@ -306,7 +316,8 @@ def load_library(path=None):
                "cwbl_search", "cwbl_pack_columns", "cwbl_unpack_columns", "cwbl_pack_members",
                "cwbl_unpack_members", "cwbl_vcoord_mean",
                "cwbl_member_sum", "cwbl_scale", "cwbl_set_kernel_timing", "cwbl_kernel_times",
-               "cwbl_set_option", "cwbl_bin_index", "cwbl_prep_info", "cwbl_finalize"):
+               "cwbl_set_option", "cwbl_bin_index", "cwbl_prep_info", "cwbl_reuse_info",
+               "cwbl_finalize"):
         getattr(lib, fn).restype = C.c_int
     return lib
 
@@ -410,6 +421,12 @@ class Core:
         """cwbl_prep_info: the search-index split of the last analyze_var (PrepInfo)."""
         info = PrepInfo()
         self._check(self.lib.cwbl_prep_info(C.byref(info)))
+        return info
+
+    def reuse_info(self):
+        """cwbl_reuse_info: what the last analyze_var solved from kept records (ReuseInfo)."""
+        info = ReuseInfo()
+        self._check(self.lib.cwbl_reuse_info(C.byref(info)))
         return info
 
     # ---- member <-> column transposes (device pointers; see cwbl/transpose.py) ----------

@@ -70,6 +70,8 @@ module letkf_core_gpu
 
     ! cwbl_set_option: the search index mode (0 host build, 1 device bins + tree on demand)
     integer(c_int), parameter, public :: CWBL_OPT_INDEX = 13
+    ! cwbl_set_option: MiB of assembled records kept for the next variable (0 = no reuse)
+    integer(c_int), parameter, public :: CWBL_OPT_RECORD_REUSE = 14
 
     type, bind(C), public :: cwbl_bin_grid         ! cwbl_bin_index
         real(c_float)  :: x0, y0, z0, binv
@@ -81,6 +83,11 @@ module letkf_core_gpu
         real(c_double) :: ms_tree, ms_bins, ms_columns, ms_tree_wait
     end type cwbl_prep_info_t
 
+    type, bind(C), public :: cwbl_reuse_info_t     ! cwbl_reuse_info
+        integer(c_long_long) :: batches_reused, batches_assembled, bytes_held
+        real(c_double)       :: ms_compare
+    end type cwbl_reuse_info_t
+
     ! projection_nml (module_config.f90:70-75), include/cwb_letkf_ingest.h
     type, bind(C), public :: cwbl_projection
         real(c_float) :: sta_lon, cen_lat, truelat1, truelat2
@@ -90,7 +97,7 @@ module letkf_core_gpu
               cwbl_pack_columns, cwbl_unpack_columns, cwbl_pack_members, cwbl_unpack_members, &
               cwbl_vcoord_mean, &
               cwbl_member_sum, cwbl_scale, cwbl_set_stream, cwbl_set_option, &
-              cwbl_bin_index, cwbl_prep_info, &
+              cwbl_bin_index, cwbl_prep_info, cwbl_reuse_info, &
               cwbl_finalize, cwbl_abi_version, cwbl_error, cwbl_check
     ! host obs ingest (include/cwb_letkf_ingest.h); file names and varname are passed as
     ! trim(name)//c_null_char
@@ -289,6 +296,12 @@ module letkf_core_gpu
             import :: c_int, cwbl_prep_info_t
             type(cwbl_prep_info_t), intent(out) :: info
         end function cwbl_prep_info
+
+        ! what the last cwbl_analyze_var solved from kept records (CWBL_OPT_RECORD_REUSE)
+        integer(c_int) function cwbl_reuse_info(info) bind(C, name='cwbl_reuse_info')
+            import :: c_int, cwbl_reuse_info_t
+            type(cwbl_reuse_info_t), intent(out) :: info
+        end function cwbl_reuse_info
 
         integer(c_int) function cwbl_finalize() bind(C, name='cwbl_finalize')
             import :: c_int

@@ -100,7 +100,11 @@ typedef struct cwbl_init_params {
                             * search batch at k = 17..40 (two buffers); at k = 65..128 the
                             * hand-off records (135 KB per point) are bounded by this value
                             * when it is given, else by min(13 GB, 40% of the device memory
-                            * free at cwbl_init), with sub-batches shrunk to fit */
+                            * free at cwbl_init), with sub-batches shrunk to fit.  The
+                            * records kept for reuse at k = 17..40 (CWBL_OPT_RECORD_REUSE:
+                            * 6.9 KB per point of the cached batches, 31 GB for a
+                            * 300 x 300 x 50 slab) have their own budget and are outside
+                            * this value too */
 } cwbl_init_params;
 
 /* One GTS platform: type(gts_structure), module_gts_omboma.f90:13-22. */
@@ -188,7 +192,8 @@ typedef struct cwbl_stats {
   int       ntrees;          /* trees built for this variable */
   int       reserved;
   double    ms_total;        /* wall time of the call */
-  double    ms_prep;         /* tree build + obs QC tables */
+  double    ms_prep;         /* tree build + obs QC tables; for a record-reuse candidate */
+                             /* (equal key) also its slab staging and coordinate compare */
   double    ms_search;       /* neighbour search kernels */
   double    ms_solve;        /* solve kernels (+ the tune_q pass when requested) */
   double    ms_copy;         /* host<->device copies of the slab (host memory only; for a */
@@ -311,12 +316,21 @@ enum {
   CWBL_OPT_MAX_BATCH = 11,     /* points per search batch, >= 256 (0 = automatic, default) */
   CWBL_OPT_INFO_WINDOW = 12,   /* points per reduction of the per-point solve info, >= 256
                                 * (0 = 2^25, default; smaller values exercise the rollover) */
-  CWBL_OPT_INDEX = 13          /* search index of the next cwbl_analyze_var: 0 k-d tree and bins
+  CWBL_OPT_INDEX = 13,         /* search index of the next cwbl_analyze_var: 0 k-d tree and bins
                                 * built on the host (default); 1 bins built on the device from
                                 * the obs coordinates, columns in obs order, the k-d tree built
                                 * by a host thread and used only where a list truncates (or
                                 * for every point with CWBL_OPT_SEARCH = 1).  Cached indexes
                                 * of the two modes are kept apart */
+  CWBL_OPT_RECORD_REUSE = 14   /* k = 17..40 record path: device memory budget in MiB for the
+                                * assembled records kept from one cwbl_analyze_var to the next
+                                * (0 = no reuse; default min(40 GiB, 40% of the device memory
+                                * free at cwbl_init)).  A call whose obs set, options, type
+                                * parameters, multi_infl, slab shape and coordinates equal the
+                                * previous call's solves from the kept records and skips the
+                                * QC columns, the search and the assembly: bit-identical
+                                * results.  A budget below the slab's need keeps the leading
+                                * batches that fit */
 };
 int         cwbl_set_option(int option, long long value);
 
@@ -355,6 +369,17 @@ typedef struct cwbl_prep_info_t {
   double ms_tree_wait;     /* CWBL_OPT_INDEX = 1: time the call waited for a tree worker */
 } cwbl_prep_info_t;
 int         cwbl_prep_info(cwbl_prep_info_t *out);
+
+/* What the last cwbl_analyze_var reused (CWBL_OPT_RECORD_REUSE). */
+typedef struct cwbl_reuse_info_t {
+  long long batches_reused;     /* search batches solved from kept records */
+  long long batches_assembled;  /* search batches that ran the search and the assembly */
+  long long bytes_held;         /* device memory of the cache: records, accepted counts and
+                                 * the coordinate snapshot */
+  double    ms_compare;         /* host time of the coordinate compare, its read-back and
+                                 * synchronisation included (0: the key already differed) */
+} cwbl_reuse_info_t;
+int         cwbl_reuse_info(cwbl_reuse_info_t *out);
 
 int         cwbl_finalize(void);
 const char *cwbl_last_error(void);
