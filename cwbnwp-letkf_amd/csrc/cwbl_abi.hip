@@ -223,6 +223,7 @@ struct TreeBufs {
 
 enum KernelId {
   KT_SEARCH_BINNED, KT_SEARCH_FLAGGED, KT_SEARCH_TREE, KT_ASSEMBLE_RECORD, KT_SOLVE_TQ40,
+  KT_SOLVE_TQ40_MULTI,
   KT_BIG_HANDOFF, KT_TQB_TAIL, KT_SOLVE_TQ, KT_SOLVE_TQ_BIG, KT_SOLVE_JACOBI, KT_TUNE_Q,
   KT_COUNT
 };
@@ -477,6 +478,7 @@ std::string kernel_name(int id) {
     case KT_SEARCH_TREE: return "search_kernel<SlabQuery>";
     case KT_ASSEMBLE_RECORD: return "assemble_record_kernel<" + std::to_string(kRecordWaves) + ">";
     case KT_SOLVE_TQ40: return "solve_tq40_kernel<" + kp + ", 0>";
+    case KT_SOLVE_TQ40_MULTI: return "solve_tq40_multi_kernel<" + kp + ">";
     case KT_BIG_HANDOFF:
       return S.kp == 128 ? "solve_tq_rows_kernel<128, 64>"
                          : "solve_tq_big_kernel<" + kp + ", false, " +
@@ -2043,6 +2045,259 @@ int cwbl_analyze_var(const cwbl_var_params *vp, const cwbl_slab *sl, cwbl_stats 
   R.batches_assembled = nbat - R.batches_reused;
   R.bytes_held = (long long)C.bytes();
   return finish();
+}
+
+// ---- cwbl_analyze_vars -----------------------------------------------------------------------
+// The group rule (include/cwb_letkf_core.h), before any device work.
+static int check_group(int nvar, const cwbl_var_params *vp, const cwbl_slab *sl) {
+  if (nvar < 1 || nvar > CWBL_MAX_GROUP_VARS)
+    return fail(CWBL_ERR_ARG, "cwbl_analyze_vars: nvar = %d, must be 1..%d", nvar,
+                CWBL_MAX_GROUP_VARS);
+  if (!vp || !sl) return fail(CWBL_ERR_ARG, "null argument");
+  const cwbl_slab &s0 = sl[0];
+  if (s0.nx < 0 || s0.ny < 0 || s0.nz < 0 || s0.ix_lim < 0 || s0.iy_lim < 0 ||
+      s0.ix_lim > s0.nx || s0.iy_lim > s0.ny || s0.ix_lim > s0.alt_nx || s0.iy_lim > s0.alt_ny)
+    return fail(CWBL_ERR_ARG, "slab bounds: nx=%d ny=%d ix_lim=%d iy_lim=%d alt=%dx%d", s0.nx,
+                s0.ny, s0.ix_lim, s0.iy_lim, s0.alt_nx, s0.alt_ny);
+  if (!(vp[0].multi_infl > 0.0f)) return fail(CWBL_ERR_ARG, "multi_infl must be > 0");
+  const size_t bvar = (size_t)s0.nx * s0.ny * s0.nz * (size_t)S.k * sizeof(float);
+  for (int i = 1; i < nvar; ++i) {
+    const cwbl_slab &s = sl[i];
+    const struct { const char *name; bool same; } f[] = {
+        {"nx", s.nx == s0.nx}, {"ny", s.ny == s0.ny}, {"nz", s.nz == s0.nz},
+        {"alt_nx", s.alt_nx == s0.alt_nx}, {"alt_ny", s.alt_ny == s0.alt_ny},
+        {"ix_lim", s.ix_lim == s0.ix_lim}, {"iy_lim", s.iy_lim == s0.iy_lim},
+        {"memory", s.memory == s0.memory}, {"x (pointer)", s.x == s0.x},
+        {"y (pointer)", s.y == s0.y}, {"alt (pointer)", s.alt == s0.alt},
+        {"multi_infl", std::memcmp(&vp[i].multi_infl, &vp[0].multi_infl, sizeof(float)) == 0},
+        {"gts", std::memcmp(vp[i].gts, vp[0].gts, sizeof vp[0].gts) == 0},
+        {"radar", std::memcmp(vp[i].radar, vp[0].radar, sizeof vp[0].radar) == 0}};
+    for (const auto &e : f)
+      if (!e.same)
+        return fail(CWBL_ERR_ARG, "cwbl_analyze_vars: variable %d differs from variable 0 in %s",
+                    i, e.name);
+  }
+  for (int i = 0; i < nvar; ++i)
+    for (int j = i + 1; j < nvar && bvar > 0; ++j) {
+      const uintptr_t a = (uintptr_t)sl[i].var, b = (uintptr_t)sl[j].var;
+      if (a < b + bvar && b < a + bvar)
+        return fail(CWBL_ERR_ARG, "cwbl_analyze_vars: the var arrays of variables %d and %d overlap",
+                    i, j);
+    }
+  return CWBL_OK;
+}
+
+// The fused path (k = 17..40 record path): per search batch and record sub-batch, as
+// cwbl_analyze_var plans them, one search, one assembly into S.wsa and one
+// solve_tq40_multi_kernel over all variables; batch b + 1's search overlaps batch b's solve.
+// The record cache is neither read, filled nor invalidated.
+static int analyze_group_fused(int nvar, const cwbl_var_params *vp, const cwbl_slab *sl,
+                               cwbl_stats &st) {
+  const cwbl_slab &s0 = sl[0];
+  const long long npts = st.points;
+  VarCall v;
+  v.vp = &vp[0];
+  v.sl = &s0;
+  v.npts = npts;
+  hipEvent_t e0, e1, e2, e_ready;
+  HIPCHK(event(0, &e0));
+  HIPCHK(hipEventRecord(e0, S.stream));
+  std::memset(&R, 0, sizeof R);
+  R.bytes_held = (long long)S.cache.bytes();
+  if (int rc = plan_trees(v)) return rc;
+  st.ntrees = v.nt;
+  if (v.nt == 0 || npts == 0) {  // `if(all(.not. succeed)) cycle` (:66)
+    HIPCHK(hipStreamSynchronize(S.stream));
+    prep_collect();
+    return CWBL_OK;
+  }
+  for (const TreeDesc &d : v.descs) st.q1_undefined += d.q1_undef ? npts : 0;
+  HIPCHK(event(1, &e1));
+  HIPCHK(hipEventRecord(e1, S.stream));
+  HIPCHK(event(2, &e2));
+  // the slab: device arrays as they are; a host slab whole, every variable into its own part
+  // of the staging buffer before the batches and back after the last solve and tune_q
+  v.L = (long long)s0.nx * s0.ny * s0.nz;
+  SlabDev &sd = v.sd;
+  sd.nx = s0.nx; sd.ny = s0.ny; sd.nz = s0.nz; sd.alt_nx = s0.alt_nx;
+  sd.alt_ny = s0.alt_ny; sd.ix_lim = s0.ix_lim; sd.iy_lim = s0.iy_lim; sd.L = v.L;
+  v.bvar = (size_t)v.L * S.k * 4;
+  v.host = s0.memory != CWBL_MEM_DEVICE;
+  Tq40Vars tv{};
+  tv.nvar = nvar;
+  for (int i = 0; i < nvar; ++i) {
+    tv.use_rtpp[i] = vp[i].use_rtpp;
+    tv.use_rtps[i] = vp[i].use_rtps;
+    tv.rtpp_alpha[i] = vp[i].rtpp_alpha;
+    tv.rtps_alpha[i] = vp[i].rtps_alpha;
+  }
+  if (!v.host) {
+    sd.x = s0.x; sd.y = s0.y; sd.alt = s0.alt;
+    for (int i = 0; i < nvar; ++i) tv.var[i] = sl[i].var;
+  } else {
+    HIPCHK(stage(S.sx, s0.x, (size_t)s0.nx * s0.ny * 4, CWBL_MEM_HOST));
+    HIPCHK(stage(S.sy, s0.y, (size_t)s0.nx * s0.ny * 4, CWBL_MEM_HOST));
+    HIPCHK(stage(S.salt, s0.alt, (size_t)s0.alt_nx * s0.alt_ny * s0.nz * 4, CWBL_MEM_HOST));
+    HIPCHK(S.svar.ensure(v.bvar * (size_t)nvar));
+    sd.x = S.sx.as<float>(); sd.y = S.sy.as<float>(); sd.alt = S.salt.as<float>();
+    for (int i = 0; i < nvar; ++i) {
+      tv.var[i] = S.svar.as<float>() + (size_t)i * (size_t)v.L * S.k;
+      if (v.bvar > 0)
+        HIPCHK(hipMemcpyAsync(tv.var[i], sl[i].var, v.bvar, hipMemcpyHostToDevice, S.stream));
+    }
+  }
+  sd.var = tv.var[0];
+  HIPCHK(hipEventRecord(e2, S.stream));
+  plan_batches(v);
+  if (int rc = alloc_call_buffers(v)) return rc;
+  HIPCHK(event(3, &e_ready));  // inputs staged and the counters cleared
+  HIPCHK(hipEventRecord(e_ready, S.stream));
+  HIPCHK(hipStreamWaitEvent(S.sstream, e_ready, 0));
+
+  const TreeDesc *dtrees = S.tdesc.as<TreeDesc>();
+  DevStats *dst = S.stats.as<DevStats>();
+  const long long nbat = (long long)v.plan.size();
+  for (long long bi = 0; bi < nbat; ++bi) {
+    const long long g0 = v.plan[bi].first;
+    const int nb = v.plan[bi].second;
+    if (g0 + nb - v.win0 > v.info_cap) {  // close the info window; S.stream orders the reuse
+      HIPCHK(launch_reduce_info(S.stream, S.info.as<int2>(), (int)(g0 - v.win0), dst));
+      v.win0 = g0;
+    }
+    int2 *const infob = S.info.as<int2>() + (g0 - v.win0);  // this batch's info
+    int *ncnt = (bi & 1) ? S.nbr_cnt2.as<int>() : S.nbr_cnt.as<int>();
+    int *nidx = (bi & 1) ? S.nbr_idx2.as<int>() : S.nbr_idx.as<int>();
+    const int ev = v.ev;
+    hipEvent_t a, b, b2, dn;
+    HIPCHK(event(ev, &a));
+    HIPCHK(event(ev + 1, &b));
+    HIPCHK(event(ev + 2, &b2));
+    HIPCHK(event(ev + 3, &dn));
+    if (int rc = search_batch(v, bi, ncnt, nidx, a, b)) return rc;
+    HIPCHK(hipStreamWaitEvent(S.stream, b, 0));
+    HIPCHK(hipEventRecord(b2, S.stream));
+    // the sub-batches of solve_batch_path's record path
+    const long long cap = std::min<long long>(S.tq4_sub > 0 ? S.tq4_sub : nb, 1 << 19);
+    const long long Bs = std::min<long long>(sub_batch(nb, cap), 1 << 19);
+    HIPCHK(S.wsa.ensure((size_t)(Bs + 1) * 8 * AsmRecord<kTq4KP>::WORDS));
+    double *rec = S.wsa.as<double>();
+    if (Bs >= nb) {  // the whole batch: timed between b2 and dn (recorded anyway)
+      auto asm_ = [&]() {
+        return launch_assemble_record(S.stream, S.kp, dtrees, v.c, sd, g0, nb, ncnt, nidx, infob,
+                                      rec);
+      };
+      auto multi = [&]() {
+        return launch_solve_tq40_multi(S.stream, S.kp, v.c, sd, tv, g0, nb, rec, infob);
+      };
+      HIPCHK(kt_pair(S.stream, b2, KT_ASSEMBLE_RECORD, nb, dn, KT_SOLVE_TQ40_MULTI, nb, asm_,
+                     multi));
+    } else {
+      for (long long s = 0; s < nb; s += Bs) {
+        const int ns = (int)std::min<long long>(Bs, nb - s);
+        int kt;
+        HIPCHK(kt_begin(S.stream, &kt));
+        HIPCHK(launch_assemble_record(S.stream, S.kp, dtrees, v.c, sd, g0 + s, ns,
+                                      ncnt + s * v.nt, nidx + s * v.list_cap, infob + s, rec));
+        HIPCHK(kt_end(S.stream, kt, KT_ASSEMBLE_RECORD, ns));
+        HIPCHK(kt_begin(S.stream, &kt));
+        HIPCHK(launch_solve_tq40_multi(S.stream, S.kp, v.c, sd, tv, g0 + s, ns, rec, infob + s));
+        HIPCHK(kt_end(S.stream, kt, KT_SOLVE_TQ40_MULTI, ns));
+      }
+    }
+    HIPCHK(hipEventRecord(dn, S.stream));  // this batch's lists are free again
+    v.search_ev.push_back({ev, ev + 1});
+    v.solve_ev.push_back({ev + 2, ev + 3});
+    v.done_ev.push_back(ev + 3);
+    v.ev += 4;
+  }
+  HIPCHK(launch_reduce_info(S.stream, S.info.as<int2>(), (int)(npts - v.win0), dst));
+  int ev = v.ev;
+  for (int i = 0; i < nvar; ++i) {  // letkf_tune_q on the variables that ask for it
+    if (!vp[i].tune_q) continue;
+    hipEvent_t a, b;
+    HIPCHK(event(ev, &a));
+    HIPCHK(event(ev + 1, &b));
+    HIPCHK(hipEventRecord(a, S.stream));
+    SlabDev sdi = sd;
+    sdi.var = tv.var[i];
+    int kt;
+    HIPCHK(kt_begin(S.stream, &kt));
+    HIPCHK(launch_tune_q(S.stream, sdi, S.k));
+    HIPCHK(kt_end(S.stream, kt, KT_TUNE_Q, npts));
+    HIPCHK(hipEventRecord(b, S.stream));
+    v.solve_ev.push_back({ev, ev + 1});
+    ev += 2;
+  }
+  hipEvent_t e_back, e_end;
+  HIPCHK(event(ev, &e_back));
+  HIPCHK(event(ev + 1, &e_end));
+  HIPCHK(hipEventRecord(e_back, S.stream));
+  if (v.host && v.bvar > 0)
+    for (int i = 0; i < nvar; ++i)
+      HIPCHK(hipMemcpyAsync(sl[i].var, tv.var[i], v.bvar, hipMemcpyDeviceToHost, S.stream));
+  HIPCHK(hipEventRecord(e_end, S.stream));
+  DevStats ds;
+  HIPCHK(hipMemcpyAsync(&ds, S.stats.p, sizeof ds, hipMemcpyDeviceToHost, S.stream));
+  HIPCHK(hipStreamSynchronize(S.stream));
+  kt_collect();
+  prep_collect();
+
+  st.solved = (long long)ds.solved;
+  st.nobs_sum = (long long)ds.nobs_sum;
+  st.lz_truncated = (long long)ds.lz_truncated;
+  st.nonconverged = (long long)ds.nonconverged;
+  st.sweeps_sum = (long long)ds.sweeps_sum;
+  st.max_p = (int)ds.max_p;
+  st.max_sweeps = (int)ds.max_sweeps;
+  st.ms_prep = elapsed(0, 1);
+  for (auto &p : v.search_ev) st.ms_search += elapsed(p.first, p.second);
+  for (auto &p : v.solve_ev) st.ms_solve += elapsed(p.first, p.second);
+  st.ms_copy = elapsed(1, 2) + (v.host ? elapsed(ev, ev + 1) : 0.0f);
+  R.batches_assembled = nbat;
+  return CWBL_OK;
+}
+
+int cwbl_analyze_vars(int nvar, const cwbl_var_params *vp, const cwbl_slab *slabs,
+                      cwbl_stats *stats) {
+  if (int rc = require_device()) return rc;
+  if (!S.have_obs) return fail(CWBL_ERR_STATE, "cwbl_set_obs has not been called");
+  if (int rc = check_group(nvar, vp, slabs)) return rc;
+  const long long npts = (long long)slabs[0].ix_lim * slabs[0].iy_lim * slabs[0].nz;
+  if (npts >= (1LL << 32))  // the kernels enumerate a slab's points in 32 bits
+    return fail(CWBL_ERR_ARG, "slab of %lld points: at most 2^32 - 1 per call", npts);
+  const auto t_start = std::chrono::steady_clock::now();
+  cwbl_stats st;
+  std::memset(&st, 0, sizeof st);
+  if (!record_path()) {
+    // every other path: the variables one after another through cwbl_analyze_var; the
+    // counters are the first variable's (they do not depend on the variable), the times summed
+    for (int i = 0; i < nvar; ++i) {
+      cwbl_stats si;
+      if (int rc = cwbl_analyze_var(&vp[i], &slabs[i], &si)) return rc;
+      if (i == 0) {
+        st = si;
+      } else {
+        st.ms_prep += si.ms_prep;
+        st.ms_search += si.ms_search;
+        st.ms_solve += si.ms_solve;
+        st.ms_copy += si.ms_copy;
+      }
+    }
+  } else {
+    if (slabs[0].memory == CWBL_MEM_DEVICE) HIPCHK(order_after_caller());
+    S.kpend.clear();  // (an earlier call that failed midway leaves nothing to collect)
+    S.kev_used = 0;
+    g_bounce_ms = 0.0;
+    std::memset(&P, 0, sizeof P);
+    g_pspans.clear();
+    g_pev_used = 0;
+    st.points = npts;
+    if (int rc = analyze_group_fused(nvar, vp, slabs, st)) return rc;
+  }
+  st.ms_total =
+      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+  if (stats) *stats = st;
+  return CWBL_OK;
 }
 
 int cwbl_solve_batch(int npts, const long long *col_off, const float *yo, const float *yb,

@@ -259,6 +259,21 @@ hipError_t launch_assemble_record(hipStream_t s, int kp, const TreeDesc *trees, 
 hipError_t launch_solve_tq40(hipStream_t s, int kp, SolveConsts c, SlabDev slab, long long g0,
                              int npts, double *ws, int2 *info);
 
+// cwbl_analyze_vars: the variables of a group share the record (A, b1) and so the factor
+// A = Q T Q^T; solve_tq40_multi_kernel (cwbl_tq40_multi.hip) tridiagonalises once per point
+// and replays the reflectors on every variable's x'.  The per-variable table goes to the
+// kernel by value; slab.var is unused there.
+constexpr int kMaxGroupVars = 8;  // = CWBL_MAX_GROUP_VARS
+struct Tq40Vars {
+  float *var[kMaxGroupVars];
+  float rtpp_alpha[kMaxGroupVars], rtps_alpha[kMaxGroupVars];
+  int use_rtpp[kMaxGroupVars], use_rtps[kMaxGroupVars];
+  int nvar;
+};
+hipError_t launch_solve_tq40_multi(hipStream_t s, int kp, SolveConsts c, SlabDev slab,
+                                   const Tq40Vars &vars, long long g0, int npts, double *ws,
+                                   int2 *info);
+
 // Split form of the KP = 128 slab path (configs[3]: k = 97..128).  solve_tq_big_kernel<128,
 // false, kBigJ0> assembles A and runs the first kBigJ0 Householder steps (4x4 register
 // blocks over 256 threads, one point per workgroup), then hands the trailing

@@ -122,7 +122,8 @@ class ReuseInfo(C.Structure):
 
 
 #: exported symbols of the product library (include/cwb_letkf_core.h)
-EXPORTS = ["cwbl_init", "cwbl_set_stream", "cwbl_set_obs", "cwbl_analyze_var", "cwbl_solve_batch", "cwbl_search",
+EXPORTS = ["cwbl_init", "cwbl_set_stream", "cwbl_set_obs", "cwbl_analyze_var", "cwbl_analyze_vars",
+           "cwbl_solve_batch", "cwbl_search",
            "cwbl_pack_columns", "cwbl_unpack_columns", "cwbl_pack_members",
            "cwbl_unpack_members", "cwbl_vcoord_mean", "cwbl_member_sum", "cwbl_scale", "cwbl_set_kernel_timing", "cwbl_kernel_times",
            "cwbl_set_option", "cwbl_bin_index", "cwbl_prep_info", "cwbl_reuse_info",
@@ -291,6 +292,8 @@ def load_library(path=None):
     lib.cwbl_set_obs.argtypes = [C.POINTER(ObsSet)]
     lib.cwbl_set_stream.argtypes = [vp]
     lib.cwbl_analyze_var.argtypes = [C.POINTER(VarParams), C.POINTER(Slab), C.POINTER(Stats)]
+    lib.cwbl_analyze_vars.argtypes = [C.c_int, C.POINTER(VarParams), C.POINTER(Slab),
+                                      C.POINTER(Stats)]
     lib.cwbl_solve_batch.argtypes = [C.c_int, vp, vp, vp, vp, C.c_float, C.c_int, C.c_float,
                                      C.c_int, C.c_float, vp, vp, C.c_int]
     lib.cwbl_search.argtypes = [C.c_int, vp, C.c_float, C.c_float, C.c_int, C.c_int, vp, vp,
@@ -312,7 +315,8 @@ def load_library(path=None):
     lib.cwbl_finalize.argtypes = []
     lib.cwbl_last_error.restype = cp
     lib.cwbl_abi_version.restype = C.c_int
-    for fn in ("cwbl_init", "cwbl_set_stream", "cwbl_set_obs", "cwbl_analyze_var", "cwbl_solve_batch",
+    for fn in ("cwbl_init", "cwbl_set_stream", "cwbl_set_obs", "cwbl_analyze_var",
+               "cwbl_analyze_vars", "cwbl_solve_batch",
                "cwbl_search", "cwbl_pack_columns", "cwbl_unpack_columns", "cwbl_pack_members",
                "cwbl_unpack_members", "cwbl_vcoord_mean",
                "cwbl_member_sum", "cwbl_scale", "cwbl_set_kernel_timing", "cwbl_kernel_times",
@@ -320,6 +324,10 @@ def load_library(path=None):
                "cwbl_finalize"):
         getattr(lib, fn).restype = C.c_int
     return lib
+
+
+#: CWBL_MAX_GROUP_VARS: most variables of one Core.analyze_vars call
+MAX_GROUP_VARS = 8
 
 
 class CwblError(RuntimeError):
@@ -364,6 +372,19 @@ class Core:
     def analyze_var(self, vp, slab):
         st = Stats()
         self._check(self.lib.cwbl_analyze_var(C.byref(vp), C.byref(slab), C.byref(st)))
+        return st
+
+    def analyze_vars(self, vps, slabs):
+        """cwbl_analyze_vars: up to MAX_GROUP_VARS variables that share a localisation (equal
+        multi_infl and type parameters, one grid: the same x, y, alt arrays) in one call.
+        vps, slabs: sequences of VarParams / Slab of equal length; returns the call's Stats."""
+        vps, slabs = list(vps), list(slabs)
+        if len(vps) != len(slabs):
+            raise ValueError("analyze_vars: as many VarParams as Slabs")
+        n = len(vps)
+        va, sa = (VarParams * max(n, 1))(*vps), (Slab * max(n, 1))(*slabs)
+        st = Stats()
+        self._check(self.lib.cwbl_analyze_vars(n, va, sa, C.byref(st)))
         return st
 
     def solve_batch(self, col_off, yo, yb, xb, inflat, use_rtpp, rtpp_alpha, use_rtps,

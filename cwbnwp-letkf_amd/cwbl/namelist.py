@@ -381,3 +381,44 @@ def var_names(cfg):
             break
         out.append(v.strip())
     return out
+
+
+# ---- groups of variables for cwbl_analyze_vars ----------------------------------------------
+_GRID_TAGS = {"U": "u", "V": "v", "W": "w", "PH": "w", "MU": "2d"}
+
+
+def grid_tag(name):
+    """The grid a WRF variable lives on: U and V on their staggered columns, W and PH on the
+    staggered levels, MU two-dimensional, everything else on the mass grid ("m")."""
+    return _GRID_TAGS.get(name.strip().upper(), "m")
+
+
+def record_key(cfg, ivar):
+    """What the weights of var_update entry ivar (1-based) depend on besides the obs and the
+    grid: multi_infl and every type's use_it, max_lz_pts, hclr, vclr, err_* and is_assim at
+    that ivar, as bytes (the library's make_record_key compares the same fields)."""
+    vp = var_params(cfg, ivar)
+    return (np.float32(vp.multi_infl).tobytes(), bytes(vp.gts), bytes(vp.radar))
+
+
+def var_groups(cfg, grid_of=None):
+    """The variables that may share a cwbl_analyze_vars call: lists of 0-based positions in
+    var_names(cfg) (ivar - 1), in var_update order.  Consecutive variables with an equal
+    record_key and an equal grid tag form a group; a group longer than abi.MAX_GROUP_VARS is
+    split.  grid_of: a callable or a mapping name -> tag (default: grid_tag); variables on
+    different grids have different points, hence different weights, and never share a call."""
+    if grid_of is None:
+        tag = grid_tag
+    elif callable(grid_of):
+        tag = grid_of
+    else:
+        tag = lambda name: grid_of.get(name, grid_tag(name))  # noqa: E731
+    groups, last = [], None
+    for i, name in enumerate(var_names(cfg)):
+        key = (tag(name), record_key(cfg, i + 1))
+        if groups and key == last and len(groups[-1]) < abi.MAX_GROUP_VARS:
+            groups[-1].append(i)
+        else:
+            groups.append([i])
+        last = key
+    return groups

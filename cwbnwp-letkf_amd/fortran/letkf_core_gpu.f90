@@ -93,7 +93,11 @@ module letkf_core_gpu
         real(c_float) :: sta_lon, cen_lat, truelat1, truelat2
     end type cwbl_projection
 
-    public :: cwbl_init, cwbl_set_obs, cwbl_analyze_var, cwbl_solve_batch, cwbl_search, &
+    ! most variables of one cwbl_analyze_vars call (CWBL_MAX_GROUP_VARS)
+    integer(c_int), parameter, public :: CWBL_MAX_GROUP_VARS = 8
+
+    public :: cwbl_init, cwbl_set_obs, cwbl_analyze_var, cwbl_analyze_vars, cwbl_solve_batch, &
+              cwbl_search, &
               cwbl_pack_columns, cwbl_unpack_columns, cwbl_pack_members, cwbl_unpack_members, &
               cwbl_vcoord_mean, &
               cwbl_member_sum, cwbl_scale, cwbl_set_stream, cwbl_set_option, &
@@ -122,6 +126,17 @@ module letkf_core_gpu
             type(cwbl_slab),       intent(in)    :: slab
             type(cwbl_stats),      intent(inout) :: stats
         end function cwbl_analyze_var
+
+        ! nvar variables that share a localisation in one call: vp(nvar), slabs(nvar) (equal
+        ! grid and x, y, alt arrays; equal multi_infl and type parameters), ONE stats
+        integer(c_int) function cwbl_analyze_vars(nvar, vp, slabs, stats) &
+                bind(C, name='cwbl_analyze_vars')
+            import :: c_int, cwbl_var_params, cwbl_slab, cwbl_stats
+            integer(c_int), value :: nvar
+            type(cwbl_var_params), intent(in)    :: vp(*)
+            type(cwbl_slab),       intent(in)    :: slabs(*)
+            type(cwbl_stats),      intent(inout) :: stats
+        end function cwbl_analyze_vars
 
         integer(c_int) function cwbl_solve_batch(npts, col_off, yo, yb, xb, inflat, use_rtpp, &
                 rtpp_alpha, use_rtps, rtps_alpha, xa, evals, memory) bind(C, name='cwbl_solve_batch')

@@ -210,6 +210,32 @@ int         cwbl_set_obs(const cwbl_obs_set *obs);
 int         cwbl_analyze_var(const cwbl_var_params *vp, const cwbl_slab *slab,
                              cwbl_stats *stats /* nullable */);
 
+/* cwbl_analyze_var for up to CWBL_MAX_GROUP_VARS variables that share a localisation, in one
+ * call.  The LETKF weights of a grid point depend on the obs, the localisation, multi_infl and
+ * the point's coordinates, not on the analysed variable; on the k = 17..40 record path the
+ * call searches, assembles and tridiagonalises once per point and applies the factor to every
+ * variable (solve_tq40_multi_kernel).  Each variable's result and the counters are those of
+ * cwbl_analyze_var on the same inputs, bit for bit.  It keeps no cache and neither reads,
+ * fills nor invalidates the record cache (CWBL_OPT_RECORD_REUSE), so it saves the same work
+ * at any grid size and memory budget.  On every other path (k <= 16, k > 40,
+ * CWBL_OPT_SOLVER = 1, CWBL_OPT_SPLIT40 = 0) the variables run one after another through
+ * cwbl_analyze_var's code.
+ *
+ * Group rule (checked before any device work; a violation returns CWBL_ERR_ARG and the message
+ * names the variable index and the field): 1 <= nvar <= CWBL_MAX_GROUP_VARS; every slabs[i]
+ * equals slabs[0] in nx, ny, nz, alt_nx, alt_ny, ix_lim, iy_lim, memory and in the x, y, alt
+ * POINTERS (the same arrays); the var ranges [var, var + nx ny nz k) are pairwise disjoint;
+ * every vp[i] equals vp[0] in multi_infl and in all gts / radar type parameters.  use_rtpp,
+ * rtpp_alpha, use_rtps, rtps_alpha and tune_q are free per variable.
+ *
+ * stats (nullable) is ONE struct: points of one slab; the counters are what cwbl_analyze_var
+ * reports for any one variable of the group; the ms_* fields are the call's own times (summed
+ * over the variables where they run one after another). */
+#define CWBL_MAX_GROUP_VARS 8
+int         cwbl_analyze_vars(int nvar, const cwbl_var_params *vp /* [nvar] */,
+                              const cwbl_slab *slabs /* [nvar] */,
+                              cwbl_stats *stats /* nullable, ONE */);
+
 /* letkf_solve for npts points (module_letkf_core.f90:598-700).  Point i uses columns
  * [col_off[i], col_off[i+1]) of yo(ncol) and yb(k,ncol) (member fastest), xb(k,npts) ->
  * xa(k,npts).  evals (nullable) receives the eigenvalues of inflat*I + yb yb^T per point in
