@@ -972,17 +972,26 @@ SolveConsts solve_consts(float inflat, int use_rtpp, float rtpp_a, int use_rtps,
   return c;
 }
 
-// ---- cwbl_analyze_var by stage ---------------------------------------------------------------
-// One call of cwbl_analyze_var (letkf_driver's per-variable body, module_letkf_core.f90:59-297):
+// ---- cwbl_analyze_var / cwbl_analyze_vars by stage -------------------------------------------
+// One call (analyze_call; letkf_driver's per-variable body, module_letkf_core.f90:59-297):
 //   plan_trees      build_tree x2 (cached per obs set) + the QC column tables   (:63-64)
 //   stage_slab      the slab in device memory (host slabs staged / piped)
 //   plan_batches    search/solve batches
 //   per batch       search_batch (S.sstream) -> solve_batch_path (S.stream), with the host
 //                   slab's var piped in and out around it (S.h2d / S.d2h)        (:209-240)
 //   finish_call     info reduction, tune_q (:253-278), write-back, statistics
+// cwbl_analyze_var is a call of one variable; the record path of cwbl_analyze_vars is a group
+// call: nvar variables that share everything but var and the epilogue's flags, so the trees,
+// the batches, the searches and the assembly are variable 0's and only the solve
+// (solve_tq40_multi_kernel), tune_q and the host slab's var see every variable.
 struct VarCall {
-  const cwbl_var_params *vp = nullptr;
-  const cwbl_slab *sl = nullptr;
+  const cwbl_var_params *vp = nullptr;  // [nvar]
+  const cwbl_slab *sl = nullptr;        // [nvar]
+  int nvar = 1;
+  bool group = false;
+  // var of every variable in device memory (a single call: var[0] = sd.var) and, for a group,
+  // the solve's table of per-variable flags
+  Tq40Vars tv{};
   long long npts = 0, L = 0;
   SlabDev sd{};
   size_t bvar = 0;
@@ -1160,14 +1169,15 @@ int stage_slab(VarCall &v) {
   const size_t balt = (size_t)sl->alt_nx * sl->alt_ny * sl->nz * 4;
   v.bvar = (size_t)v.L * S.k * 4;
   v.host = sl->memory != CWBL_MEM_DEVICE;
-  v.piped = v.host && sl->ix_lim == sl->nx && sl->iy_lim == sl->ny;
+  // (a group's host slabs move whole, from wherever they lie: not piped, page-locked or bounced)
+  v.piped = !v.group && v.host && sl->ix_lim == sl->nx && sl->iy_lim == sl->ny;
   v.piped_back = v.piped && !v.vp->tune_q;  // tune_q touches the whole slab afterwards
   // pageable var (a Fortran host's ordinary arrays): copies from pageable memory are staged by
   // the runtime and do not overlap.  It is page-locked in place for the call (r4, C2 from
   // pageable numpy arrays: 58.7 M pts/s, against 58.2 M page-locked and 50.8 M through the
   // bounce slots, whose host copies stall the pipeline); the slots remain the fallback when
   // the registration fails (and CWBL_OPT_PAGEABLE = 1 forces them)
-  v.bounce = v.host && v.bvar > 0 && !host_pinned(sl->var);
+  v.bounce = !v.group && v.host && v.bvar > 0 && !host_pinned(sl->var);
   if (v.bounce && S.pageable_register) {
     if (hipHostRegister(sl->var, v.bvar, hipHostRegisterDefault) == hipSuccess) {
       v.registered = true;
@@ -1177,16 +1187,23 @@ int stage_slab(VarCall &v) {
     }
   }
   if (!v.host) {
-    sd.x = sl->x; sd.y = sl->y; sd.alt = sl->alt; sd.var = sl->var;
-    return CWBL_OK;
+    sd.x = sl->x; sd.y = sl->y; sd.alt = sl->alt;
+    for (int i = 0; i < v.nvar; ++i) v.tv.var[i] = v.sl[i].var;
+  } else {
+    HIPCHK(stage(S.sx, sl->x, bxy, CWBL_MEM_HOST));
+    HIPCHK(stage(S.sy, sl->y, bxy, CWBL_MEM_HOST));
+    HIPCHK(stage(S.salt, sl->alt, balt, CWBL_MEM_HOST));
+    sd.x = S.sx.as<float>(); sd.y = S.sy.as<float>(); sd.alt = S.salt.as<float>();
+    // every variable has its own part of S.svar; var comes up here unless the batches pipe it
+    // or stage_bounce moves it
+    HIPCHK(S.svar.ensure(v.bvar * (size_t)v.nvar));
+    for (int i = 0; i < v.nvar; ++i) {
+      v.tv.var[i] = S.svar.as<float>() + (size_t)i * (size_t)v.L * S.k;
+      if (v.bvar > 0 && !v.piped && !v.bounce)
+        HIPCHK(hipMemcpyAsync(v.tv.var[i], v.sl[i].var, v.bvar, hipMemcpyHostToDevice, S.stream));
+    }
   }
-  HIPCHK(stage(S.sx, sl->x, bxy, CWBL_MEM_HOST));
-  HIPCHK(stage(S.sy, sl->y, bxy, CWBL_MEM_HOST));
-  HIPCHK(stage(S.salt, sl->alt, balt, CWBL_MEM_HOST));
-  if (v.piped || v.bounce) HIPCHK(S.svar.ensure(v.bvar));
-  else HIPCHK(stage(S.svar, sl->var, v.bvar, CWBL_MEM_HOST));
-  sd.x = S.sx.as<float>(); sd.y = S.sy.as<float>(); sd.alt = S.salt.as<float>();
-  sd.var = S.svar.as<float>();
+  sd.var = v.tv.var[0];
   return CWBL_OK;
 }
 
@@ -1443,7 +1460,8 @@ long long sub_batch(int nb, long long cap) {
 
 // letkf_yoyb + letkf_solve (module_letkf_core.f90:300-700) for batch (g0, nb) on S.stream, one
 // path per ensemble-size class:
-//   k = 17..40   record path: assemble_record_kernel -> record -> solve_tq40_kernel
+//   k = 17..40   record path: assemble_record_kernel -> record -> solve_tq40_kernel, or
+//                solve_tq40_multi_kernel for a group call
 //   k = 65..128  hand-off path: 256-thread kernel (assembly + first steps) -> record ->
 //                solve_tqb_tail_kernel; CWBL_OPT_BIG_PATH = 0: one 256-thread kernel
 //   otherwise    one wavefront per point: solve_tq_kernel; CWBL_OPT_SOLVER = 1: the Jacobi
@@ -1461,7 +1479,7 @@ int solve_batch_path(VarCall &v, long long g0, int nb, const int *ncnt, const in
   int kt;
   const bool handoff = (S.kp == 96 || S.kp == kBigSplitKP) && S.big_split &&
                        S.k > big_split_j0(S.kp) + 2;
-  if (S.tq4 && S.kp == kTq4KP && !S.jacobi) {
+  if (record_path()) {
     // (Bs <= 2^19: the solve addresses a sub-batch's records with 32-bit byte offsets)
     const long long cap = std::min<long long>(S.tq4_sub > 0 ? S.tq4_sub : nb, 1 << 19);
     const long long Bs = std::min<long long>(sub_batch(nb, cap), 1 << 19);
@@ -1470,9 +1488,15 @@ int solve_batch_path(VarCall &v, long long g0, int nb, const int *ncnt, const in
     double *rec = crec ? crec : S.wsa.as<double>();
     // a cached batch keeps every sub-batch's records, S.wsa only the current one's
     const size_t rstep = crec ? AsmRecord<kTq4KP>::WORDS : 0;
+    // the solve of n points from g: one variable's, or the group's over all its variables
+    const int kt_solve = v.group ? KT_SOLVE_TQ40_MULTI : KT_SOLVE_TQ40;
+    auto solve = [&](long long g, int n, double *r, int2 *inf) {
+      return v.group ? launch_solve_tq40_multi(S.stream, S.kp, c, sd, v.tv, g, n, r, inf)
+                     : launch_solve_tq40(S.stream, S.kp, c, sd, g, n, r, inf);
+    };
     if (Bs >= nb && hit) {
-      if (S.ktiming) S.kpend.push_back({KT_SOLVE_TQ40, b2, dn, nb});
-      HIPCHK(launch_solve_tq40(S.stream, S.kp, c, sd, g0, nb, rec, infob));
+      if (S.ktiming) S.kpend.push_back({kt_solve, b2, dn, nb});
+      HIPCHK(solve(g0, nb, rec, infob));
       return CWBL_OK;
     }
     if (Bs >= nb) {  // the whole batch: timed between b2 and dn (recorded anyway)
@@ -1480,8 +1504,8 @@ int solve_batch_path(VarCall &v, long long g0, int nb, const int *ncnt, const in
         return launch_assemble_record(S.stream, S.kp, dtrees, c, sd, g0, nb, ncnt, nidx, infob,
                                       rec);
       };
-      auto tq40 = [&]() { return launch_solve_tq40(S.stream, S.kp, c, sd, g0, nb, rec, infob); };
-      HIPCHK(kt_pair(S.stream, b2, KT_ASSEMBLE_RECORD, nb, dn, KT_SOLVE_TQ40, nb, asm_, tq40));
+      auto tq40 = [&]() { return solve(g0, nb, rec, infob); };
+      HIPCHK(kt_pair(S.stream, b2, KT_ASSEMBLE_RECORD, nb, dn, kt_solve, nb, asm_, tq40));
       return CWBL_OK;
     }
     for (long long s0 = 0; s0 < nb; s0 += Bs) {
@@ -1494,8 +1518,8 @@ int solve_batch_path(VarCall &v, long long g0, int nb, const int *ncnt, const in
         HIPCHK(kt_end(S.stream, kt, KT_ASSEMBLE_RECORD, ns));
       }
       HIPCHK(kt_begin(S.stream, &kt));
-      HIPCHK(launch_solve_tq40(S.stream, S.kp, c, sd, g0 + s0, ns, srec, infob + s0));
-      HIPCHK(kt_end(S.stream, kt, KT_SOLVE_TQ40, ns));
+      HIPCHK(solve(g0 + s0, ns, srec, infob + s0));
+      HIPCHK(kt_end(S.stream, kt, kt_solve, ns));
     }
     return CWBL_OK;
   }
@@ -1549,14 +1573,17 @@ int finish_call(VarCall &v, cwbl_stats &st) {
     if (int rc = keep_info(v, v.npts)) return rc;
   }
   int ev = v.ev;
-  if (v.vp->tune_q) {
+  for (int i = 0; i < v.nvar; ++i) {  // letkf_tune_q on the variables that ask for it
+    if (!v.vp[i].tune_q) continue;
     hipEvent_t a, b;
     HIPCHK(event(ev, &a));
     HIPCHK(event(ev + 1, &b));
     HIPCHK(hipEventRecord(a, S.stream));
+    SlabDev sdi = v.sd;
+    sdi.var = v.tv.var[i];
     int kt;
     HIPCHK(kt_begin(S.stream, &kt));
-    HIPCHK(launch_tune_q(S.stream, v.sd, S.k));
+    HIPCHK(launch_tune_q(S.stream, sdi, S.k));
     HIPCHK(kt_end(S.stream, kt, KT_TUNE_Q, v.npts));
     HIPCHK(hipEventRecord(b, S.stream));
     v.solve_ev.push_back({ev, ev + 1});
@@ -1566,7 +1593,8 @@ int finish_call(VarCall &v, cwbl_stats &st) {
   HIPCHK(event(ev, &e_end));
   HIPCHK(event(ev + 1, &e_back));
   if (v.host && !v.piped_back && !v.bounce)
-    HIPCHK(hipMemcpyAsync(v.sl->var, S.svar.p, v.bvar, hipMemcpyDeviceToHost, S.stream));
+    for (int i = 0; i < v.nvar; ++i)
+      HIPCHK(hipMemcpyAsync(v.sl[i].var, v.tv.var[i], v.bvar, hipMemcpyDeviceToHost, S.stream));
   if (v.piped_back) {  // the call returns after the last batch's copy back
     HIPCHK(hipEventRecord(e_back, S.d2h));
     HIPCHK(hipStreamWaitEvent(S.stream, e_back, 0));
@@ -1881,9 +1909,9 @@ int cwbl_set_obs(const cwbl_obs_set *o) {
   return CWBL_OK;
 }
 
-int cwbl_analyze_var(const cwbl_var_params *vp, const cwbl_slab *sl, cwbl_stats *stats) {
-  if (int rc = require_device()) return rc;
-  if (!S.have_obs) return fail(CWBL_ERR_STATE, "cwbl_set_obs has not been called");
+// The argument checks of a call's slab and parameters (a group: of its variable 0), before
+// any device work.
+static int check_slab(const cwbl_var_params *vp, const cwbl_slab *sl) {
   if (!vp || !sl) return fail(CWBL_ERR_ARG, "null argument");
   if (sl->nx < 0 || sl->ny < 0 || sl->nz < 0 || sl->ix_lim < 0 || sl->iy_lim < 0 ||
       sl->ix_lim > sl->nx || sl->iy_lim > sl->ny || sl->ix_lim > sl->alt_nx ||
@@ -1891,31 +1919,47 @@ int cwbl_analyze_var(const cwbl_var_params *vp, const cwbl_slab *sl, cwbl_stats 
     return fail(CWBL_ERR_ARG, "slab bounds: nx=%d ny=%d ix_lim=%d iy_lim=%d alt=%dx%d",
                 sl->nx, sl->ny, sl->ix_lim, sl->iy_lim, sl->alt_nx, sl->alt_ny);
   if (!(vp->multi_infl > 0.0f)) return fail(CWBL_ERR_ARG, "multi_infl must be > 0");
+  const long long npts = (long long)sl->ix_lim * sl->iy_lim * sl->nz;
+  if (npts >= (1LL << 32))  // the kernels enumerate a slab's points in 32 bits
+    return fail(CWBL_ERR_ARG, "slab of %lld points: at most 2^32 - 1 per call", npts);
+  return CWBL_OK;
+}
+
+// The call is ordered behind the caller's work on a device slab, and the per-call counters
+// and spans start empty.
+static int begin_call(const cwbl_slab *sl) {
   if (sl->memory == CWBL_MEM_DEVICE) HIPCHK(order_after_caller());
-  const auto t_start = std::chrono::steady_clock::now();
   S.kpend.clear();  // (an earlier call that failed midway leaves nothing to collect)
   S.kev_used = 0;
   g_bounce_ms = 0.0;
   std::memset(&P, 0, sizeof P);
+  std::memset(&R, 0, sizeof R);
   g_pspans.clear();
   g_pev_used = 0;
+  return CWBL_OK;
+}
+
+// The driver of cwbl_analyze_var and of the record path of cwbl_analyze_vars (v.vp, v.sl, and
+// for a group v.nvar, v.group and the flags of v.tv are the caller's; the arguments are
+// checked).  A group call runs with record reuse off: the cache is not read, filled or
+// invalidated.
+static int analyze_call(VarCall &v, cwbl_stats *stats) {
+  const cwbl_var_params *vp = v.vp;
+  const cwbl_slab *sl = v.sl;
+  if (int rc = begin_call(sl)) return rc;
+  const auto t_start = std::chrono::steady_clock::now();
   cwbl_stats st;
   std::memset(&st, 0, sizeof st);
   const long long npts = (long long)sl->ix_lim * sl->iy_lim * sl->nz;
-  if (npts >= (1LL << 32))  // the kernels enumerate a slab's points in 32 bits
-    return fail(CWBL_ERR_ARG, "slab of %lld points: at most 2^32 - 1 per call", npts);
-  st.points = npts;
+  st.points = v.npts = npts;
+  RecordCache &C = S.cache;
   auto finish = [&]() {
+    R.bytes_held = (long long)C.bytes();
     st.ms_total =
         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
     if (stats) *stats = st;
     return CWBL_OK;
   };
-
-  VarCall v;
-  v.vp = vp;
-  v.sl = sl;
-  v.npts = npts;
   struct Unregister {  // a page-locked-in-place var, on every return path, once no queued
     VarCall &v;        // copy can still touch it
     ~Unregister() {
@@ -1933,9 +1977,7 @@ int cwbl_analyze_var(const cwbl_var_params *vp, const cwbl_slab *sl, cwbl_stats 
   HIPCHK(hipEventRecord(e0, S.stream));
   // Record reuse: an equal key makes the call a candidate; the coordinates decide.  (A
   // candidate stages its slab first, so its ms_prep holds the staging and the compare.)
-  RecordCache &C = S.cache;
-  std::memset(&R, 0, sizeof R);
-  const bool reuse_on = record_path() && S.reuse_budget > 0 && npts > 0;
+  const bool reuse_on = !v.group && record_path() && S.reuse_budget > 0 && npts > 0;
   RecordKey key;
   bool staged = false;
   if (reuse_on) {
@@ -2043,8 +2085,17 @@ int cwbl_analyze_var(const cwbl_var_params *vp, const cwbl_slab *sl, cwbl_stats 
   }
   R.batches_reused = v.reuse == 2 ? v.ncached : 0;
   R.batches_assembled = nbat - R.batches_reused;
-  R.bytes_held = (long long)C.bytes();
   return finish();
+}
+
+int cwbl_analyze_var(const cwbl_var_params *vp, const cwbl_slab *sl, cwbl_stats *stats) {
+  if (int rc = require_device()) return rc;
+  if (!S.have_obs) return fail(CWBL_ERR_STATE, "cwbl_set_obs has not been called");
+  if (int rc = check_slab(vp, sl)) return rc;
+  VarCall v;
+  v.vp = vp;
+  v.sl = sl;
+  return analyze_call(v, stats);
 }
 
 // ---- cwbl_analyze_vars -----------------------------------------------------------------------
@@ -2053,13 +2104,8 @@ static int check_group(int nvar, const cwbl_var_params *vp, const cwbl_slab *sl)
   if (nvar < 1 || nvar > CWBL_MAX_GROUP_VARS)
     return fail(CWBL_ERR_ARG, "cwbl_analyze_vars: nvar = %d, must be 1..%d", nvar,
                 CWBL_MAX_GROUP_VARS);
-  if (!vp || !sl) return fail(CWBL_ERR_ARG, "null argument");
+  if (int rc = check_slab(vp, sl)) return rc;
   const cwbl_slab &s0 = sl[0];
-  if (s0.nx < 0 || s0.ny < 0 || s0.nz < 0 || s0.ix_lim < 0 || s0.iy_lim < 0 ||
-      s0.ix_lim > s0.nx || s0.iy_lim > s0.ny || s0.ix_lim > s0.alt_nx || s0.iy_lim > s0.alt_ny)
-    return fail(CWBL_ERR_ARG, "slab bounds: nx=%d ny=%d ix_lim=%d iy_lim=%d alt=%dx%d", s0.nx,
-                s0.ny, s0.ix_lim, s0.iy_lim, s0.alt_nx, s0.alt_ny);
-  if (!(vp[0].multi_infl > 0.0f)) return fail(CWBL_ERR_ARG, "multi_infl must be > 0");
   const size_t bvar = (size_t)s0.nx * s0.ny * s0.nz * (size_t)S.k * sizeof(float);
   for (int i = 1; i < nvar; ++i) {
     const cwbl_slab &s = sl[i];
@@ -2087,212 +2133,44 @@ static int check_group(int nvar, const cwbl_var_params *vp, const cwbl_slab *sl)
   return CWBL_OK;
 }
 
-// The fused path (k = 17..40 record path): per search batch and record sub-batch, as
-// cwbl_analyze_var plans them, one search, one assembly into S.wsa and one
-// solve_tq40_multi_kernel over all variables; batch b + 1's search overlaps batch b's solve.
-// The record cache is neither read, filled nor invalidated.
-static int analyze_group_fused(int nvar, const cwbl_var_params *vp, const cwbl_slab *sl,
-                               cwbl_stats &st) {
-  const cwbl_slab &s0 = sl[0];
-  const long long npts = st.points;
-  VarCall v;
-  v.vp = &vp[0];
-  v.sl = &s0;
-  v.npts = npts;
-  hipEvent_t e0, e1, e2, e_ready;
-  HIPCHK(event(0, &e0));
-  HIPCHK(hipEventRecord(e0, S.stream));
-  std::memset(&R, 0, sizeof R);
-  R.bytes_held = (long long)S.cache.bytes();
-  if (int rc = plan_trees(v)) return rc;
-  st.ntrees = v.nt;
-  if (v.nt == 0 || npts == 0) {  // `if(all(.not. succeed)) cycle` (:66)
-    HIPCHK(hipStreamSynchronize(S.stream));
-    prep_collect();
-    return CWBL_OK;
-  }
-  for (const TreeDesc &d : v.descs) st.q1_undefined += d.q1_undef ? npts : 0;
-  HIPCHK(event(1, &e1));
-  HIPCHK(hipEventRecord(e1, S.stream));
-  HIPCHK(event(2, &e2));
-  // the slab: device arrays as they are; a host slab whole, every variable into its own part
-  // of the staging buffer before the batches and back after the last solve and tune_q
-  v.L = (long long)s0.nx * s0.ny * s0.nz;
-  SlabDev &sd = v.sd;
-  sd.nx = s0.nx; sd.ny = s0.ny; sd.nz = s0.nz; sd.alt_nx = s0.alt_nx;
-  sd.alt_ny = s0.alt_ny; sd.ix_lim = s0.ix_lim; sd.iy_lim = s0.iy_lim; sd.L = v.L;
-  v.bvar = (size_t)v.L * S.k * 4;
-  v.host = s0.memory != CWBL_MEM_DEVICE;
-  Tq40Vars tv{};
-  tv.nvar = nvar;
-  for (int i = 0; i < nvar; ++i) {
-    tv.use_rtpp[i] = vp[i].use_rtpp;
-    tv.use_rtps[i] = vp[i].use_rtps;
-    tv.rtpp_alpha[i] = vp[i].rtpp_alpha;
-    tv.rtps_alpha[i] = vp[i].rtps_alpha;
-  }
-  if (!v.host) {
-    sd.x = s0.x; sd.y = s0.y; sd.alt = s0.alt;
-    for (int i = 0; i < nvar; ++i) tv.var[i] = sl[i].var;
-  } else {
-    HIPCHK(stage(S.sx, s0.x, (size_t)s0.nx * s0.ny * 4, CWBL_MEM_HOST));
-    HIPCHK(stage(S.sy, s0.y, (size_t)s0.nx * s0.ny * 4, CWBL_MEM_HOST));
-    HIPCHK(stage(S.salt, s0.alt, (size_t)s0.alt_nx * s0.alt_ny * s0.nz * 4, CWBL_MEM_HOST));
-    HIPCHK(S.svar.ensure(v.bvar * (size_t)nvar));
-    sd.x = S.sx.as<float>(); sd.y = S.sy.as<float>(); sd.alt = S.salt.as<float>();
-    for (int i = 0; i < nvar; ++i) {
-      tv.var[i] = S.svar.as<float>() + (size_t)i * (size_t)v.L * S.k;
-      if (v.bvar > 0)
-        HIPCHK(hipMemcpyAsync(tv.var[i], sl[i].var, v.bvar, hipMemcpyHostToDevice, S.stream));
-    }
-  }
-  sd.var = tv.var[0];
-  HIPCHK(hipEventRecord(e2, S.stream));
-  plan_batches(v);
-  if (int rc = alloc_call_buffers(v)) return rc;
-  HIPCHK(event(3, &e_ready));  // inputs staged and the counters cleared
-  HIPCHK(hipEventRecord(e_ready, S.stream));
-  HIPCHK(hipStreamWaitEvent(S.sstream, e_ready, 0));
-
-  const TreeDesc *dtrees = S.tdesc.as<TreeDesc>();
-  DevStats *dst = S.stats.as<DevStats>();
-  const long long nbat = (long long)v.plan.size();
-  for (long long bi = 0; bi < nbat; ++bi) {
-    const long long g0 = v.plan[bi].first;
-    const int nb = v.plan[bi].second;
-    if (g0 + nb - v.win0 > v.info_cap) {  // close the info window; S.stream orders the reuse
-      HIPCHK(launch_reduce_info(S.stream, S.info.as<int2>(), (int)(g0 - v.win0), dst));
-      v.win0 = g0;
-    }
-    int2 *const infob = S.info.as<int2>() + (g0 - v.win0);  // this batch's info
-    int *ncnt = (bi & 1) ? S.nbr_cnt2.as<int>() : S.nbr_cnt.as<int>();
-    int *nidx = (bi & 1) ? S.nbr_idx2.as<int>() : S.nbr_idx.as<int>();
-    const int ev = v.ev;
-    hipEvent_t a, b, b2, dn;
-    HIPCHK(event(ev, &a));
-    HIPCHK(event(ev + 1, &b));
-    HIPCHK(event(ev + 2, &b2));
-    HIPCHK(event(ev + 3, &dn));
-    if (int rc = search_batch(v, bi, ncnt, nidx, a, b)) return rc;
-    HIPCHK(hipStreamWaitEvent(S.stream, b, 0));
-    HIPCHK(hipEventRecord(b2, S.stream));
-    // the sub-batches of solve_batch_path's record path
-    const long long cap = std::min<long long>(S.tq4_sub > 0 ? S.tq4_sub : nb, 1 << 19);
-    const long long Bs = std::min<long long>(sub_batch(nb, cap), 1 << 19);
-    HIPCHK(S.wsa.ensure((size_t)(Bs + 1) * 8 * AsmRecord<kTq4KP>::WORDS));
-    double *rec = S.wsa.as<double>();
-    if (Bs >= nb) {  // the whole batch: timed between b2 and dn (recorded anyway)
-      auto asm_ = [&]() {
-        return launch_assemble_record(S.stream, S.kp, dtrees, v.c, sd, g0, nb, ncnt, nidx, infob,
-                                      rec);
-      };
-      auto multi = [&]() {
-        return launch_solve_tq40_multi(S.stream, S.kp, v.c, sd, tv, g0, nb, rec, infob);
-      };
-      HIPCHK(kt_pair(S.stream, b2, KT_ASSEMBLE_RECORD, nb, dn, KT_SOLVE_TQ40_MULTI, nb, asm_,
-                     multi));
-    } else {
-      for (long long s = 0; s < nb; s += Bs) {
-        const int ns = (int)std::min<long long>(Bs, nb - s);
-        int kt;
-        HIPCHK(kt_begin(S.stream, &kt));
-        HIPCHK(launch_assemble_record(S.stream, S.kp, dtrees, v.c, sd, g0 + s, ns,
-                                      ncnt + s * v.nt, nidx + s * v.list_cap, infob + s, rec));
-        HIPCHK(kt_end(S.stream, kt, KT_ASSEMBLE_RECORD, ns));
-        HIPCHK(kt_begin(S.stream, &kt));
-        HIPCHK(launch_solve_tq40_multi(S.stream, S.kp, v.c, sd, tv, g0 + s, ns, rec, infob + s));
-        HIPCHK(kt_end(S.stream, kt, KT_SOLVE_TQ40_MULTI, ns));
-      }
-    }
-    HIPCHK(hipEventRecord(dn, S.stream));  // this batch's lists are free again
-    v.search_ev.push_back({ev, ev + 1});
-    v.solve_ev.push_back({ev + 2, ev + 3});
-    v.done_ev.push_back(ev + 3);
-    v.ev += 4;
-  }
-  HIPCHK(launch_reduce_info(S.stream, S.info.as<int2>(), (int)(npts - v.win0), dst));
-  int ev = v.ev;
-  for (int i = 0; i < nvar; ++i) {  // letkf_tune_q on the variables that ask for it
-    if (!vp[i].tune_q) continue;
-    hipEvent_t a, b;
-    HIPCHK(event(ev, &a));
-    HIPCHK(event(ev + 1, &b));
-    HIPCHK(hipEventRecord(a, S.stream));
-    SlabDev sdi = sd;
-    sdi.var = tv.var[i];
-    int kt;
-    HIPCHK(kt_begin(S.stream, &kt));
-    HIPCHK(launch_tune_q(S.stream, sdi, S.k));
-    HIPCHK(kt_end(S.stream, kt, KT_TUNE_Q, npts));
-    HIPCHK(hipEventRecord(b, S.stream));
-    v.solve_ev.push_back({ev, ev + 1});
-    ev += 2;
-  }
-  hipEvent_t e_back, e_end;
-  HIPCHK(event(ev, &e_back));
-  HIPCHK(event(ev + 1, &e_end));
-  HIPCHK(hipEventRecord(e_back, S.stream));
-  if (v.host && v.bvar > 0)
-    for (int i = 0; i < nvar; ++i)
-      HIPCHK(hipMemcpyAsync(sl[i].var, tv.var[i], v.bvar, hipMemcpyDeviceToHost, S.stream));
-  HIPCHK(hipEventRecord(e_end, S.stream));
-  DevStats ds;
-  HIPCHK(hipMemcpyAsync(&ds, S.stats.p, sizeof ds, hipMemcpyDeviceToHost, S.stream));
-  HIPCHK(hipStreamSynchronize(S.stream));
-  kt_collect();
-  prep_collect();
-
-  st.solved = (long long)ds.solved;
-  st.nobs_sum = (long long)ds.nobs_sum;
-  st.lz_truncated = (long long)ds.lz_truncated;
-  st.nonconverged = (long long)ds.nonconverged;
-  st.sweeps_sum = (long long)ds.sweeps_sum;
-  st.max_p = (int)ds.max_p;
-  st.max_sweeps = (int)ds.max_sweeps;
-  st.ms_prep = elapsed(0, 1);
-  for (auto &p : v.search_ev) st.ms_search += elapsed(p.first, p.second);
-  for (auto &p : v.solve_ev) st.ms_solve += elapsed(p.first, p.second);
-  st.ms_copy = elapsed(1, 2) + (v.host ? elapsed(ev, ev + 1) : 0.0f);
-  R.batches_assembled = nbat;
-  return CWBL_OK;
-}
-
 int cwbl_analyze_vars(int nvar, const cwbl_var_params *vp, const cwbl_slab *slabs,
                       cwbl_stats *stats) {
   if (int rc = require_device()) return rc;
   if (!S.have_obs) return fail(CWBL_ERR_STATE, "cwbl_set_obs has not been called");
   if (int rc = check_group(nvar, vp, slabs)) return rc;
-  const long long npts = (long long)slabs[0].ix_lim * slabs[0].iy_lim * slabs[0].nz;
-  if (npts >= (1LL << 32))  // the kernels enumerate a slab's points in 32 bits
-    return fail(CWBL_ERR_ARG, "slab of %lld points: at most 2^32 - 1 per call", npts);
+  if (record_path()) {
+    // the fused path: per search batch and record sub-batch one search, one assembly and one
+    // solve_tq40_multi_kernel over all variables
+    VarCall v;
+    v.vp = vp;
+    v.sl = slabs;
+    v.nvar = nvar;
+    v.group = true;
+    v.tv.nvar = nvar;
+    for (int i = 0; i < nvar; ++i) {
+      v.tv.use_rtpp[i] = vp[i].use_rtpp;
+      v.tv.use_rtps[i] = vp[i].use_rtps;
+      v.tv.rtpp_alpha[i] = vp[i].rtpp_alpha;
+      v.tv.rtps_alpha[i] = vp[i].rtps_alpha;
+    }
+    return analyze_call(v, stats);
+  }
+  // every other path: the variables one after another through cwbl_analyze_var; the
+  // counters are the first variable's (they do not depend on the variable), the times summed
   const auto t_start = std::chrono::steady_clock::now();
   cwbl_stats st;
   std::memset(&st, 0, sizeof st);
-  if (!record_path()) {
-    // every other path: the variables one after another through cwbl_analyze_var; the
-    // counters are the first variable's (they do not depend on the variable), the times summed
-    for (int i = 0; i < nvar; ++i) {
-      cwbl_stats si;
-      if (int rc = cwbl_analyze_var(&vp[i], &slabs[i], &si)) return rc;
-      if (i == 0) {
-        st = si;
-      } else {
-        st.ms_prep += si.ms_prep;
-        st.ms_search += si.ms_search;
-        st.ms_solve += si.ms_solve;
-        st.ms_copy += si.ms_copy;
-      }
+  for (int i = 0; i < nvar; ++i) {
+    cwbl_stats si;
+    if (int rc = cwbl_analyze_var(&vp[i], &slabs[i], &si)) return rc;
+    if (i == 0) {
+      st = si;
+    } else {
+      st.ms_prep += si.ms_prep;
+      st.ms_search += si.ms_search;
+      st.ms_solve += si.ms_solve;
+      st.ms_copy += si.ms_copy;
     }
-  } else {
-    if (slabs[0].memory == CWBL_MEM_DEVICE) HIPCHK(order_after_caller());
-    S.kpend.clear();  // (an earlier call that failed midway leaves nothing to collect)
-    S.kev_used = 0;
-    g_bounce_ms = 0.0;
-    std::memset(&P, 0, sizeof P);
-    g_pspans.clear();
-    g_pev_used = 0;
-    st.points = npts;
-    if (int rc = analyze_group_fused(nvar, vp, slabs, st)) return rc;
   }
   st.ms_total =
       std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();

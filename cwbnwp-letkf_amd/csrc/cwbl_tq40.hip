@@ -25,83 +25,20 @@
 // they eliminated.  Nothing is written to global memory but the analysis, and the kernel
 // spills no registers (244 VGPRs, two waves per SIMD, 19.4 KB of LDS per wave).  Every loop
 // over steps, slots and columns is compile-time (sfor), so all register indices are static.
-#include "cwbl_device.h"
+//
+// What solve_tq40_multi_kernel (cwbl_tq40_multi.hip) runs as well is in cwbl_tq40_common.h:
+// the layout constants and the shared-memory struct, the row sums, dlarfg, the point decode,
+// the record load, the trace and the wave's quadrature rounds.  Phase 1, phase 2 and the
+// back-transform below are this kernel's own; the multi kernel has its b1-only twins.  The
+// quadrature (level loop, round loop, d) and the RTPP/RTPS epilogue stand in both files, the
+// same text: as shared functions they cost solve_tq40_multi_kernel 2 % per launch.
+#include "cwbl_tq40_common.h"
 
 #include <utility>
 
 namespace cwbl {
 
 namespace {
-
-// Rank-2 updates run in groups of kUG columns, each group's first products before its second
-// ones, so no fused FMA reads the accumulator the one before it wrote (the compiler puts an
-// s_nop between two inline-asm statements that share a register); the matvec keeps kNA
-// partial sums per row (column c -> sum c % kNA).  r6 A/B of the alternatives:
-// profiles/r6_tq40_ab.txt.
-constexpr int kUG = 8;
-constexpr int kNA = 2;
-template <int NS>
-__device__ __forceinline__ double acc_sum(const double (&pa)[kNA][NS], int r) {
-  return pa[0][r] + pa[1][r];
-}
-
-// Sum over this lane's 16-lane row, the same value on every lane: two quad_perm stages (two
-// v_mov_b32_dpp and a v_add_f64 each: gfx950 has no 64-bit quad_perm), then the four quad
-// sums Q0 + Q4 + Q8 + Q12 as one row_newbcast move and three fused v_fmac_f64_dpp (x 1.0,
-// one rounding each, as an add): 10 VALU instructions instead of row16_sum's 12.  The quad
-// sum is read by DPP two or more wait states after its add (the move's own hazard nop).
-__device__ __forceinline__ double rsum16(double v) {
-  v += dpp_f64<0xB1>(v);  // quad_perm [1,0,3,2]
-  v += dpp_f64<0x4E>(v);  // quad_perm [2,3,0,1]
-  double s = rbcast<0>(v);
-  s = fmac_row<4>(s, v, 1.0);
-  s = fmac_row<8>(s, v, 1.0);
-  return fmac_row<12>(s, v, 1.0);
-}
-
-// Three row sums, stage by stage: each stage's DPP reads come three instructions after the
-// adds that feed them, so no wait states are needed between the stages (the same sums, the
-// same rounding order as rsum16)
-__device__ __forceinline__ void rsum16x3(double &a, double &b, double &c) {
-  a += dpp_f64<0xB1>(a);
-  b += dpp_f64<0xB1>(b);
-  c += dpp_f64<0xB1>(c);
-  a += dpp_f64<0x4E>(a);
-  b += dpp_f64<0x4E>(b);
-  c += dpp_f64<0x4E>(c);
-  double sa = rbcast<0>(a), sb = rbcast<0>(b), sc = rbcast<0>(c);
-  sa = fmac_row<4>(sa, a, 1.0);
-  sb = fmac_row<4>(sb, b, 1.0);
-  sc = fmac_row<4>(sc, c, 1.0);
-  sa = fmac_row<8>(sa, a, 1.0);
-  sb = fmac_row<8>(sb, b, 1.0);
-  sc = fmac_row<8>(sc, c, 1.0);
-  a = fmac_row<12>(sa, a, 1.0);
-  b = fmac_row<12>(sb, b, 1.0);
-  c = fmac_row<12>(sc, c, 1.0);
-}
-
-// N row sums stage by stage (rsum16x3's interleaving for the prefix rows' column sums; the
-// same rounding order as rsum16)
-template <int N>
-__device__ __forceinline__ void rsum16xN(double (&a)[N]) {
-  double s[N];
-  sfor<N>([&](auto ii) { a[decltype(ii)::value] += dpp_f64<0xB1>(a[decltype(ii)::value]); });
-  sfor<N>([&](auto ii) { a[decltype(ii)::value] += dpp_f64<0x4E>(a[decltype(ii)::value]); });
-  sfor<N>([&](auto ii) { s[decltype(ii)::value] = rbcast<0>(a[decltype(ii)::value]); });
-  sfor<N>([&](auto ii) {
-    constexpr int i = decltype(ii)::value;
-    s[i] = fmac_row<4>(s[i], a[i], 1.0);
-  });
-  sfor<N>([&](auto ii) {
-    constexpr int i = decltype(ii)::value;
-    s[i] = fmac_row<8>(s[i], a[i], 1.0);
-  });
-  sfor<N>([&](auto ii) {
-    constexpr int i = decltype(ii)::value;
-    a[i] = fmac_row<12>(s[i], a[i], 1.0);
-  });
-}
 
 // STOP = 6 (a timing bound; wrong results): the matvec and rank-2 update skip the 16-column
 // blocks right of a slot's rows (trailing column tc >= 16 (r + 1)), i.e. the products a
@@ -112,30 +49,15 @@ constexpr bool upper_free(int r, int tc) { return STOP == 6 && tc >= 16 * (r + 1
 
 }  // namespace
 
-template <int KP>
-struct Tq40Smem {
-  double pv[4][kTq40J0][KP];  // phase 1's reflectors, column j by row (rows <= j + 1 unused)
-  double qs[4][KP];           // per quadrature round: sum over the round's nodes of omega x(row)
-  double qz[4][KP + 1];       // T^-1 u2 (slot 7 of the last round); [KP]: other lanes' dump
-  double tq[4][KP + 1][4];    // d_i, c(i-1,i), (Q^T b1)_i, (Q^T x')_i
-  double tau[4][KP];
-};
-
 // STOP > 0: timing-ablation instantiations (CWBL_DEBUG_TQ_STOP = 5: the record loads only,
 // 4: after the first J0 steps, 2: after the tridiagonalisation, 3: after the quadrature; var
-// is not written), so
-// that the production kernel's code is not perturbed by the early exits
+// is not written), so that the production kernel's code is not perturbed by the early exits
 template <int KP, int STOP = 0>
 __global__ void __launch_bounds__(64, 2)
 solve_tq40_kernel(SolveConsts c, SlabDev slab, long long g0, int npts,
                   double *__restrict__ ws, int2 *__restrict__ info) {
-  using HO = AsmRecord<KP>;
-  constexpr int J0 = kTq40J0;         // steps with the prefix block (phase 1)
-  constexpr int KT = KP - J0;         // slot rows J0 + l + 16 r
-  constexpr int NS = KT / 16;         // row slots per lane
-  constexpr int NV = NS + 1;          // vector slots: 0 = rows l < J0, 1.. = row slots
-  constexpr int H = KP / 2;           // rows walked by each side of a twisted solve
-  static_assert(KT % 16 == 0 && J0 <= 16 && J0 >= 2 && KP % 2 == 0, "tq40 layout");
+  using LY = Tq40Layout<KP>;
+  constexpr int J0 = LY::J0, KT = LY::KT, NS = LY::NS, NV = LY::NV, H = LY::H;
   using SM = Tq40Smem<KP>;
   __shared__ SM sm;
 
@@ -147,39 +69,9 @@ solve_tq40_kernel(SolveConsts c, SlabDev slab, long long g0, int npts,
   const bool valid = gi < npts;
   const int k = c.k;
   const int ptot = valid ? info[gi].x : 0;
-  // record words of this point: SGPR base + 32-bit offset (the host keeps a batch's records
-  // below 2^32 bytes).  A lane past the batch reads the spare record npts (the host
-  // allocates npts + 1)
-  const unsigned wb = (unsigned)(valid ? gi : npts) * (unsigned)HO::WORDS;
-  auto w = [&](int i) { return gld(ws, wb + (unsigned)i); };
-  auto apk = [](int r, int col) {  // packed lower index of A(r, col)
-    return col <= r ? r * (r + 1) / 2 + col : col * (col + 1) / 2 + r;
-  };
-  // global row of vector slot vs (rows that do not exist get KP + 1: never < k)
-  auto vrow = [&](int vs) { return vs == 0 ? (l < J0 ? l : KP + 1) : J0 + l + 16 * (vs - 1); };
+  auto vrow = [&](int vs) { return tq40_vrow<KP>(l, vs); };
+  const long long P = tq40_var_index(slab, g0, valid ? gi : 0);  // var index of member 0
 
-  // var index of member 0 (g = i + ix_lim (j + iy_lim kz); g < 2^32: var would exceed HBM first)
-  long long P = 0;
-  {
-    const unsigned g = (unsigned)(g0 + (valid ? gi : 0));
-    const unsigned ix = (unsigned)slab.ix_lim, iy = (unsigned)slab.iy_lim;
-    const unsigned rr = g / ix, ii = g - rr * ix, kz = rr / iy, jj = rr - kz * iy;
-    P = ii + (long long)slab.nx * (jj + (long long)slab.ny * kz);
-  }
-
-  // fp32 sum over members in member order; member m is row m: prefix slot lane m (m < J0),
-  // else row slot (m - J0) / 16, lane (m - J0) % 16.  Every caller's x is +0 on the rows past
-  // k, and s + 0 = s (s is never -0), so the rows past k need no mask and each term is one
-  // v_add_f32 with a row_newbcast source.
-  auto seq_sum_f32 = [&](const float (&x)[NV]) {
-    float s = 0.0f;
-    sfor<KP>([&](auto mm) {
-      constexpr int m = decltype(mm)::value;
-      constexpr int vs = m < J0 ? 0 : 1 + (m - J0) / 16, ln = m < J0 ? m : (m - J0) % 16;
-      s = s + rbcast<ln>(x[vs]);
-    });
-    return s;
-  };
   // ---- background of the point: member i = row i --------------------------------------------
   float xbl[NV];
   double xb_mean;
@@ -192,7 +84,7 @@ solve_tq40_kernel(SolveConsts c, SlabDev slab, long long g0, int npts,
       xbl[vs] = mem ? xv : 0.0f;
     });
     // sum(xb) * nmember_inv (:671)
-    xb_mean = (double)(seq_sum_f32(xbl) * c.nmember_inv);
+    xb_mean = (double)(seq_sum_f32<KP>(xbl) * c.nmember_inv);
   }
 
   // ---- A from the record ---------------------------------------------------------------------
@@ -201,51 +93,12 @@ solve_tq40_kernel(SolveConsts c, SlabDev slab, long long g0, int npts,
   const int lp = l < J0 ? l : 0;
   const bool pre = l < J0;
   double uxP, ubP, ux[NS], ub[NS];
-  // A(t, col) of row t = J0 + l + 16 r: packed word tri(t) + col where col <= t, tri(col) + t
-  // above.  A column at or left of the slot's first row is in the lower part on every lane, one
-  // right of its last row in the upper part: one lane base plus a compile-time offset each,
-  // and only the columns inside the slot's row range pick per lane.  The loads go through a
-  // buffer resource on the wave's four records (a lane past the batch reads the spare record
-  // npts, at most three records on), so the compile-time part of each offset sits in the
-  // instruction's offset fields instead of a per-load address computation.  (r6, measured and
-  // dropped: staging the records through LDS with coalesced 16-byte loads — equal at best,
-  // the per-lane gathers cost latency, not address throughput.)
-  const __amdgpu_buffer_rsrc_t rs = rec_rsrc(ws + (size_t)(4 * g4) * HO::WORDS, 4 * HO::WORDS);
-  const unsigned rq = (unsigned)(valid ? q : npts - 4 * g4) * (unsigned)HO::WORDS;
-  auto rw = [&](unsigned vword, unsigned cword) {  // record word vword + cword (cword static)
-    const auto v = __builtin_amdgcn_raw_buffer_load_b64(rs, (int)(8u * vword), (int)(8u * cword), 0);
-    return __longlong_as_double(((long long)v[1] << 32) | (unsigned)v[0]);
-  };
-  sfor<NS>([&](auto rr) {
-    constexpr int r = decltype(rr)::value;
-    constexpr int T0 = J0 + 16 * r, T1 = T0 + 15;  // the slot's rows
-    const int t = T0 + l;
-    const unsigned lo = rq + (unsigned)(HO::TA + t * (t + 1) / 2), up = rq + (unsigned)(HO::TA + t);
-    sfor<KP>([&](auto cc) {
-      constexpr int col = decltype(cc)::value;
-      constexpr unsigned tc = (unsigned)(col * (col + 1) / 2);
-      if constexpr (col <= T0) A[r][col] = rw(lo, col);
-      else if constexpr (col > T1) A[r][col] = rw(up, tc);
-      else A[r][col] = rw(col <= t ? lo + col : up + tc, 0u);
-    });
-  });
-  {
-    const unsigned lo = rq + (unsigned)(HO::TA + lp * (lp + 1) / 2), up = rq + (unsigned)(HO::TA + lp);
-    sfor<J0>([&](auto cc) {
-      constexpr int col = decltype(cc)::value;
-      Pb[col] = rw(col <= lp ? lo + col : up + (unsigned)(col * (col + 1) / 2), 0u);
-    });
-  }
-  {
-    const double b = w(HO::U1 + lp);
-    ubP = pre ? b : 0.0;
-  }
+  tq40_load_record<KP>(ws, g4, q, l, valid, npts, A, Pb, ubP, ub);
   // x' (fp64, :671-672) and b1 = Yb d; both become Q^T x', Q^T b1
   uxP = pre && l < k ? (double)xbl[0] - xb_mean : 0.0;
   sfor<NS>([&](auto rr) {
     constexpr int r = decltype(rr)::value;
     const int t = J0 + l + 16 * r;
-    ub[r] = w(HO::U1 + t);
     ux[r] = t < k ? (double)xbl[r + 1] - xb_mean : 0.0;
   });
 
@@ -260,23 +113,6 @@ solve_tq40_kernel(SolveConsts c, SlabDev slab, long long g0, int npts,
     if (valid && l == 0) info[gi] = make_int2(ptot, (int)acc);
     return;
   }
-  // dlarfg with fp64 rcp/rsq refined to ~1 ulp; H = I when x = 0 (tau = 0, v = e_j+1)
-  struct Refl {
-    double beta, tau, scal;
-  };
-  auto dlarfg = [](double alpha, double xx) {
-    const double a2 = fma(alpha, alpha, xx);
-    const double rs = rsq64(a2);  // 1/|beta|
-    const bool nz = xx > 0.0;
-    const double bt = -copysign(a2 * rs, alpha);
-    Refl h;
-    h.beta = nz ? bt : alpha;
-    h.tau = nz ? (bt - alpha) * -copysign(rs, alpha) : 0.0;
-    const double rab = rcp64(alpha - bt);
-    h.scal = nz ? rab : 0.0;
-    return h;
-  };
-
   // ---- phase 1: Householder steps 0 .. J0-1 with the prefix block -------------------------
   sfor<J0>([&](auto jj) {
     constexpr int j = decltype(jj)::value, J1 = j + 1;
@@ -405,9 +241,9 @@ solve_tq40_kernel(SolveConsts c, SlabDev slab, long long g0, int npts,
     double wPp = wP;
     dpp_pin(wPp);
     sfor<NS>([&](auto rr) { dpp_pin(wv[decltype(rr)::value]); });
-    // Columns go in pairs, each pair's first products before its second ones, so that no
-    // fmac reads the accumulator the fmac just before it wrote (the compiler puts an s_nop
-    // between two inline-asm statements that share a register)
+    // Columns go in groups of kUG, each group's first products before its second ones, so
+    // that no fmac reads the accumulator the fmac just before it wrote (the compiler puts an
+    // s_nop between two inline-asm statements that share a register)
     sfor<(KP - J1 + kUG - 1) / kUG>([&](auto pp) {
       constexpr int c0 = J1 + kUG * decltype(pp)::value;
       sfor<2>([&](auto hh) {  // hh = 0: A - wv v_c; hh = 1: - v w_c (the reference's order)
@@ -515,13 +351,11 @@ solve_tq40_kernel(SolveConsts c, SlabDev slab, long long g0, int npts,
       double wv[NS];
       sfor<NS>([&](auto rr) {
         constexpr int r = decltype(rr)::value;
-        const int t = l + 16 * r;
-        (void)t;  // rows <= j: as in phase 1
-        wv[r] = fma(-0.5 * tau * s1, v[r], tau * pp[r]);
+        wv[r] = fma(-0.5 * tau * s1, v[r], tau * pp[r]);  // rows <= j: as in phase 1
       });
       // A <- A - v w^T - w v^T on the trailing rows and columns
       sfor<NS>([&](auto rr) { dpp_pin(wv[decltype(rr)::value]); });
-      // column pairs, first products before second ones (as in phase 1)
+      // groups of kUG columns, first products before second ones (as in phase 1)
       sfor<(KT - J1 + kUG - 1) / kUG>([&](auto pp) {
         constexpr int c0 = J1 + kUG * decltype(pp)::value;
         sfor<2>([&](auto hh) {
@@ -559,18 +393,7 @@ solve_tq40_kernel(SolveConsts c, SlabDev slab, long long g0, int npts,
     sm.tq[q][KP][1] = 0.0;
   }
   __syncthreads();
-  // trace of T (= trace of A) over the members, from the diagonal in LDS: summed here, not
-  // step by step, so that no step's d_j stays live to the end
-  double trace;
-  {
-    double tp = 0.0;
-    sfor<(KP + 15) / 16>([&](auto rr) {
-      constexpr int r = decltype(rr)::value;
-      const int i = l + 16 * r;
-      if (16 * r + 15 < KP || i < KP) tp += i < k ? sm.tq[q][i < KP ? i : 0][0] : 0.0;
-    });
-    trace = rsum16(tp);
-  }
+  const double trace = tq40_trace(sm, q, l, k);
 
   if constexpr (STOP == 2) {  // timing ablation: tridiagonalisation only
     if (valid && l == 0) info[gi] = make_int2(ptot, (int)(trace + ux[1]));
@@ -583,6 +406,8 @@ solve_tq40_kernel(SolveConsts c, SlabDev slab, long long g0, int npts,
   // side l >> 3 walks rows 0..H-1 (top) or KP-1..H (bottom); slot 7 of the last round solves
   // T^-1 u2.  Each row's sum over the round's 8 nodes is an 8-lane DPP reduction; its lane 0
   // hands it to the row's owner through LDS.
+  // (Twin: the level loop, the round loop and d below are solve_tq40_multi_kernel's too, in
+  // cwbl_tq40_multi.hip: as shared functions they compile to other code)
   const double m = (double)c.inflat;
   const double ratio = trace / m - (double)(k - 1);
   int level = 1;
@@ -591,10 +416,7 @@ solve_tq40_kernel(SolveConsts c, SlabDev slab, long long g0, int npts,
     dec *= 10.0;
     ++level;
   }
-  // rounds of 8 nodes: the wave's largest need (quad_rounds) over its four points, with the
-  // (8 R - 1)-node rule of each point's own level; slot 7 of the last round is T^-1 u2
-  const int rp = quad_rounds(level);
-  const int R = __ballot(rp == 8) ? 8 : __ballot(rp == 4) ? 4 : __ballot(rp == 3) ? 3 : 2;
+  const int R = tq40_wave_rounds(level);
   const int NQ = 8 * R - 1;  // (R is wave-uniform)
   const double2 *qtab = quad_rule(c.quad_r, R, level);
   const int side = l >> 3, n8 = l & 7;
@@ -738,6 +560,7 @@ solve_tq40_kernel(SolveConsts c, SlabDev slab, long long g0, int npts,
   });
 
   // ---- analysis and RTPP / RTPS (:675-698), fp32 in the reference's order ----------------
+  // (twin: solve_tq40_multi_kernel's epilogue, with the flags and alphas of its variable)
   const double sk = sqrt((double)(k - 1));
   float xa[NV];
   sfor<NV>([&](auto vv) {
@@ -745,7 +568,7 @@ solve_tq40_kernel(SolveConsts c, SlabDev slab, long long g0, int npts,
     xa[vs] = vrow(vs) < k ? (float)(xb_mean + (d + sk * y[vs])) : 0.0f;
   });
   if (c.use_rtpp || c.use_rtps) {
-    const float xa_mean = seq_sum_f32(xa) * c.nmember_inv;
+    const float xa_mean = seq_sum_f32<KP>(xa) * c.nmember_inv;
     double xpl[NV];
     float xap[NV];
     sfor<NV>([&](auto vv) {
@@ -774,7 +597,7 @@ solve_tq40_kernel(SolveConsts c, SlabDev slab, long long g0, int npts,
         constexpr int vs = decltype(vv)::value;
         sq[vs] = xap[vs] * xap[vs];
       });
-      const float xa_std = seq_sum_f32(sq);
+      const float xa_std = seq_sum_f32<KP>(sq);
       const float f = c.rtps_alpha * sqrtf(xb_std / xa_std) - c.rtps_alpha + 1.0f;
       sfor<NV>([&](auto vv) { xap[decltype(vv)::value] = xap[decltype(vv)::value] * f; });
     }

@@ -21,7 +21,15 @@
 // project builds with -ffp-contract=off and the steps use explicit fma), so each variable's
 // analysis equals solve_tq40_kernel's on the same record bit for bit.  The loop body is the
 // same code for every variable: all register indices stay static.
-#include "cwbl_device.h"
+//
+// Shared with solve_tq40_kernel through cwbl_tq40_common.h: the layout constants and the
+// shared-memory struct, the row sums, dlarfg, the point decode, the record load, the trace and
+// the wave's quadrature rounds.  This file's own: the b1-only tridiagonalisation that keeps x
+// and scal (its matvec and rank-2 update repeat cwbl_tq40.hip's phase 1 and phase 2, which
+// carry x' as well and keep x scal), the replay, and the back-transform from x and scal.  The
+// quadrature (level loop, round loop, d) and the RTPP/RTPS epilogue repeat cwbl_tq40.hip's
+// text: as shared functions they cost this kernel 2 % per launch at eight variables.
+#include "cwbl_tq40_common.h"
 
 #include <utility>
 
@@ -29,48 +37,7 @@ namespace cwbl {
 
 namespace {
 
-// (as in cwbl_tq40.hip)
-constexpr int kUG = 8;
-constexpr int kNA = 2;
-template <int NS>
-__device__ __forceinline__ double acc_sum(const double (&pa)[kNA][NS], int r) {
-  return pa[0][r] + pa[1][r];
-}
-
-// Sum over this lane's 16-lane row, the same value on every lane (cwbl_tq40.hip's rsum16: two
-// quad_perm stages, then the four quad sums as one row_newbcast move and three fused
-// v_fmac_f64_dpp)
-__device__ __forceinline__ double rsum16(double v) {
-  v += dpp_f64<0xB1>(v);  // quad_perm [1,0,3,2]
-  v += dpp_f64<0x4E>(v);  // quad_perm [2,3,0,1]
-  double s = rbcast<0>(v);
-  s = fmac_row<4>(s, v, 1.0);
-  s = fmac_row<8>(s, v, 1.0);
-  return fmac_row<12>(s, v, 1.0);
-}
-
-// N row sums stage by stage (the same rounding order as rsum16)
-template <int N>
-__device__ __forceinline__ void rsum16xN(double (&a)[N]) {
-  double s[N];
-  sfor<N>([&](auto ii) { a[decltype(ii)::value] += dpp_f64<0xB1>(a[decltype(ii)::value]); });
-  sfor<N>([&](auto ii) { a[decltype(ii)::value] += dpp_f64<0x4E>(a[decltype(ii)::value]); });
-  sfor<N>([&](auto ii) { s[decltype(ii)::value] = rbcast<0>(a[decltype(ii)::value]); });
-  sfor<N>([&](auto ii) {
-    constexpr int i = decltype(ii)::value;
-    s[i] = fmac_row<4>(s[i], a[i], 1.0);
-  });
-  sfor<N>([&](auto ii) {
-    constexpr int i = decltype(ii)::value;
-    s[i] = fmac_row<8>(s[i], a[i], 1.0);
-  });
-  sfor<N>([&](auto ii) {
-    constexpr int i = decltype(ii)::value;
-    a[i] = fmac_row<12>(s[i], a[i], 1.0);
-  });
-}
-
-// Two row sums (the steps' x.x and x.b1; cwbl_tq40.hip's rsum16x3 without the x' sum)
+// Two row sums (the steps' x.x and x.b1: rsum16x3 without the x' sum)
 __device__ __forceinline__ void rsum16x2(double &a, double &b) {
   double ab[2] = {a, b};
   rsum16xN(ab);
@@ -92,28 +59,12 @@ __device__ __forceinline__ long long touched(long long x) {
 }  // namespace
 
 template <int KP>
-struct Tq40MultiSmem {
-  // phase 1's reflectors, column j by row, UNSCALED; [q][j][0]: the step's scal; [q][j][1]:
-  // the dump word of the lanes that hold no prefix row (rows <= j + 1 are unused)
-  double pv[4][kTq40J0][KP];
-  double qs[4][KP];           // per quadrature round: sum over the round's nodes of omega x(row)
-  double qz[4][KP + 1];       // T^-1 u2 (slot 7 of the last round); [KP]: other lanes' dump
-  double tq[4][KP + 1][4];    // d_i, c(i-1,i), (Q^T b1)_i, (Q^T x')_i of the current variable
-  double tau[4][KP];
-};
-
-template <int KP>
 __global__ void __launch_bounds__(64, 2)
 solve_tq40_multi_kernel(SolveConsts c, SlabDev slab, Tq40Vars vars, long long g0, int npts,
                         double *__restrict__ ws, int2 *__restrict__ info) {
-  using HO = AsmRecord<KP>;
-  constexpr int J0 = kTq40J0;         // steps with the prefix block (phase 1)
-  constexpr int KT = KP - J0;         // slot rows J0 + l + 16 r
-  constexpr int NS = KT / 16;         // row slots per lane
-  constexpr int NV = NS + 1;          // vector slots: 0 = rows l < J0, 1.. = row slots
-  constexpr int H = KP / 2;           // rows walked by each side of a twisted solve
-  static_assert(KT % 16 == 0 && J0 <= 16 && J0 >= 2 && KP % 2 == 0, "tq40 layout");
-  using SM = Tq40MultiSmem<KP>;
+  using LY = Tq40Layout<KP>;
+  constexpr int J0 = LY::J0, KT = LY::KT, NS = LY::NS, NV = LY::NV, H = LY::H;
+  using SM = Tq40Smem<KP>;
   __shared__ SM sm;
 
   const int lane = threadIdx.x, q = lane >> 4, l = lane & 15;
@@ -123,90 +74,16 @@ solve_tq40_multi_kernel(SolveConsts c, SlabDev slab, Tq40Vars vars, long long g0
   const bool valid = gi < npts;
   const int k = c.k;
   const int ptot = valid ? info[gi].x : 0;
-  // A lane past the batch reads the spare record npts (the host allocates npts + 1)
-  const unsigned wb = (unsigned)(valid ? gi : npts) * (unsigned)HO::WORDS;
-  auto w = [&](int i) { return gld(ws, wb + (unsigned)i); };
-  // global row of vector slot vs (rows that do not exist get KP + 1: never < k)
-  auto vrow = [&](int vs) { return vs == 0 ? (l < J0 ? l : KP + 1) : J0 + l + 16 * (vs - 1); };
+  auto vrow = [&](int vs) { return tq40_vrow<KP>(l, vs); };
+  const long long P = tq40_var_index(slab, g0, valid ? gi : 0);  // var index of member 0
 
-  // var index of member 0 (g = i + ix_lim (j + iy_lim kz); g < 2^32: var would exceed HBM first)
-  long long P = 0;
-  {
-    const unsigned g = (unsigned)(g0 + (valid ? gi : 0));
-    const unsigned ix = (unsigned)slab.ix_lim, iy = (unsigned)slab.iy_lim;
-    const unsigned rr = g / ix, ii = g - rr * ix, kz = rr / iy, jj = rr - kz * iy;
-    P = ii + (long long)slab.nx * (jj + (long long)slab.ny * kz);
-  }
-
-  // fp32 sum over members in member order (solve_tq40_kernel's seq_sum_f32)
-  auto seq_sum_f32 = [&](const float (&x)[NV]) {
-    float s = 0.0f;
-    sfor<KP>([&](auto mm) {
-      constexpr int m = decltype(mm)::value;
-      constexpr int vs = m < J0 ? 0 : 1 + (m - J0) / 16, ln = m < J0 ? m : (m - J0) % 16;
-      s = s + rbcast<ln>(x[vs]);
-    });
-    return s;
-  };
-
-  // ---- A from the record (as solve_tq40_kernel) ------------------------------------------
+  // ---- A and b1 from the record ---------------------------------------------------------------
   double A[NS][KP];  // slot rows, all columns
   double Pb[J0];     // prefix block row l (lanes >= J0 hold row 0's copy, never used)
   const int lp = l < J0 ? l : 0;
   const bool pre = l < J0;
   double ubP, ub[NS];
-  const __amdgpu_buffer_rsrc_t rs = rec_rsrc(ws + (size_t)(4 * g4) * HO::WORDS, 4 * HO::WORDS);
-  const unsigned rq = (unsigned)(valid ? q : npts - 4 * g4) * (unsigned)HO::WORDS;
-  auto rw = [&](unsigned vword, unsigned cword) {  // record word vword + cword (cword static)
-    const auto v = __builtin_amdgcn_raw_buffer_load_b64(rs, (int)(8u * vword), (int)(8u * cword), 0);
-    return __longlong_as_double(((long long)v[1] << 32) | (unsigned)v[0]);
-  };
-  sfor<NS>([&](auto rr) {
-    constexpr int r = decltype(rr)::value;
-    constexpr int T0 = J0 + 16 * r, T1 = T0 + 15;  // the slot's rows
-    const int t = T0 + l;
-    const unsigned lo = rq + (unsigned)(HO::TA + t * (t + 1) / 2), up = rq + (unsigned)(HO::TA + t);
-    sfor<KP>([&](auto cc) {
-      constexpr int col = decltype(cc)::value;
-      constexpr unsigned tc = (unsigned)(col * (col + 1) / 2);
-      if constexpr (col <= T0) A[r][col] = rw(lo, col);
-      else if constexpr (col > T1) A[r][col] = rw(up, tc);
-      else A[r][col] = rw(col <= t ? lo + col : up + tc, 0u);
-    });
-  });
-  {
-    const unsigned lo = rq + (unsigned)(HO::TA + lp * (lp + 1) / 2), up = rq + (unsigned)(HO::TA + lp);
-    sfor<J0>([&](auto cc) {
-      constexpr int col = decltype(cc)::value;
-      Pb[col] = rw(col <= lp ? lo + col : up + (unsigned)(col * (col + 1) / 2), 0u);
-    });
-  }
-  {
-    const double b = w(HO::U1 + lp);
-    ubP = pre ? b : 0.0;
-  }
-  sfor<NS>([&](auto rr) {
-    constexpr int r = decltype(rr)::value;
-    const int t = J0 + l + 16 * r;
-    ub[r] = w(HO::U1 + t);
-  });
-
-  // dlarfg with fp64 rcp/rsq refined to ~1 ulp; H = I when x = 0 (tau = 0, v = e_j+1)
-  struct Refl {
-    double beta, tau, scal;
-  };
-  auto dlarfg = [](double alpha, double xx) {
-    const double a2 = fma(alpha, alpha, xx);
-    const double rs = rsq64(a2);  // 1/|beta|
-    const bool nz = xx > 0.0;
-    const double bt = -copysign(a2 * rs, alpha);
-    Refl h;
-    h.beta = nz ? bt : alpha;
-    h.tau = nz ? (bt - alpha) * -copysign(rs, alpha) : 0.0;
-    const double rab = rcp64(alpha - bt);
-    h.scal = nz ? rab : 0.0;
-    return h;
-  };
+  tq40_load_record<KP>(ws, g4, q, l, valid, npts, A, Pb, ubP, ub);
 
   // ---- phase 1: Householder steps 0 .. J0-1 with the prefix block (b1 only) ---------------
   sfor<J0>([&](auto jj) {
@@ -249,8 +126,9 @@ solve_tq40_multi_kernel(SolveConsts c, SlabDev slab, Tq40Vars vars, long long g0
     const double xsP = xP * h.scal;
     double vP = (pre && l == J1) ? 1.0 : xsP;
     double v[NS];
-    // the reflector is final: x goes to LDS unscaled, for the replays and the back-transform
-    // (prefix rows 0, 1 and the lanes >= J0, whose x is 0, write the dump word, row 1), and
+    // the reflector is final: x goes to LDS UNSCALED, for the replays and the back-transform
+    // (sm.pv[q][j]: rows <= j + 1 of a column are unused, so word 0 takes the step's scal and
+    // word 1 is the dump word of prefix rows 0, 1 and the lanes >= J0, whose x is 0), and
     // column j's registers are dead from here on
     sm.pv[q][j][(pre && l > 1) ? l : 1] = xP;
     sfor<NS>([&](auto rr) {
@@ -463,19 +341,10 @@ solve_tq40_multi_kernel(SolveConsts c, SlabDev slab, Tq40Vars vars, long long g0
     sm.tq[q][KP][1] = 0.0;
   }
   __syncthreads();
-  // trace of T (= trace of A) over the members, from the diagonal in LDS
-  double trace;
-  {
-    double tp = 0.0;
-    sfor<(KP + 15) / 16>([&](auto rr) {
-      constexpr int r = decltype(rr)::value;
-      const int i = l + 16 * r;
-      if (16 * r + 15 < KP || i < KP) tp += i < k ? sm.tq[q][i < KP ? i : 0][0] : 0.0;
-    });
-    trace = rsum16(tp);
-  }
+  const double trace = tq40_trace(sm, q, l, k);
 
-  // ---- the quadrature rule of the point (solve_tq40_kernel): T only, once ------------------
+  // ---- the quadrature rule of the point: T only, once ---------------------------------------
+  // (twin: this level loop and the walk's LDS offsets below are solve_tq40_kernel's)
   const double m = (double)c.inflat;
   const double ratio = trace / m - (double)(k - 1);
   int level = 1;
@@ -484,8 +353,7 @@ solve_tq40_multi_kernel(SolveConsts c, SlabDev slab, Tq40Vars vars, long long g0
     dec *= 10.0;
     ++level;
   }
-  const int rp = quad_rounds(level);
-  const int R = __ballot(rp == 8) ? 8 : __ballot(rp == 4) ? 4 : __ballot(rp == 3) ? 3 : 2;
+  const int R = tq40_wave_rounds(level);
   const int NQ = 8 * R - 1;  // (R is wave-uniform)
   const double2 *qtab = quad_rule(c.quad_r, R, level);
   const int side = l >> 3, n8 = l & 7;
@@ -537,7 +405,7 @@ solve_tq40_multi_kernel(SolveConsts c, SlabDev slab, Tq40Vars vars, long long g0
         xbl[vs] = mem ? xv : 0.0f;
       });
       // sum(xb) * nmember_inv (:671)
-      xb_mean = (double)(seq_sum_f32(xbl) * c.nmember_inv);
+      xb_mean = (double)(seq_sum_f32<KP>(xbl) * c.nmember_inv);
     }
     // x' (fp64, :671-672)
     double uxP = pre && l < k ? (double)xbl[0] - xb_mean : 0.0, ux[NS];
@@ -610,7 +478,7 @@ solve_tq40_multi_kernel(SolveConsts c, SlabDev slab, Tq40Vars vars, long long g0
     });
     __syncthreads();
 
-    // ---- T^-1/2 u2 by quadrature, T^-1 u2 exactly (solve_tq40_kernel) ---------------------
+    // ---- T^-1/2 u2 by quadrature, T^-1 u2 exactly (twin: solve_tq40_kernel's round loop) ---
     double ys[NV], z[NV];
     sfor<NV>([&](auto vv) { ys[decltype(vv)::value] = 0.0; });
     for (int round = 0; round < R; ++round) {
@@ -738,13 +606,14 @@ solve_tq40_multi_kernel(SolveConsts c, SlabDev slab, Tq40Vars vars, long long g0
     });
 
     // ---- analysis and RTPP / RTPS (:675-698), fp32 in the reference's order --------------
+    // (twin: solve_tq40_kernel's epilogue, whose flags and alphas come from SolveConsts)
     float xa[NV];
     sfor<NV>([&](auto vv) {
       constexpr int vs = decltype(vv)::value;
       xa[vs] = vrow(vs) < k ? (float)(xb_mean + (d + sk * y[vs])) : 0.0f;
     });
     if (use_rtpp || use_rtps) {
-      const float xa_mean = seq_sum_f32(xa) * c.nmember_inv;
+      const float xa_mean = seq_sum_f32<KP>(xa) * c.nmember_inv;
       double xpl[NV];
       float xap[NV];
       sfor<NV>([&](auto vv) {
@@ -773,7 +642,7 @@ solve_tq40_multi_kernel(SolveConsts c, SlabDev slab, Tq40Vars vars, long long g0
           constexpr int vs = decltype(vv)::value;
           sq[vs] = xap[vs] * xap[vs];
         });
-        const float xa_std = seq_sum_f32(sq);
+        const float xa_std = seq_sum_f32<KP>(sq);
         const float f = rtps_alpha * sqrtf(xb_std / xa_std) - rtps_alpha + 1.0f;
         sfor<NV>([&](auto vv) { xap[decltype(vv)::value] = xap[decltype(vv)::value] * f; });
       }
