@@ -223,7 +223,7 @@ struct TreeBufs {
 
 enum KernelId {
   KT_SEARCH_BINNED, KT_SEARCH_FLAGGED, KT_SEARCH_TREE, KT_ASSEMBLE_RECORD, KT_SOLVE_TQ40,
-  KT_SOLVE_TQ40_MULTI,
+  KT_SOLVE_TQ40_MULTI, KT_SOLVE_TQ_MULTI2, KT_SOLVE_TQ_MULTI4, KT_SOLVE_TQ_MULTI8,
   KT_BIG_HANDOFF, KT_TQB_TAIL, KT_SOLVE_TQ, KT_SOLVE_TQ_BIG, KT_SOLVE_JACOBI, KT_TUNE_Q,
   KT_COUNT
 };
@@ -487,6 +487,9 @@ std::string kernel_name(int id) {
       return "solve_tqb_tail_kernel<" + kp + ", " + std::to_string(big_split_j0(S.kp)) +
              (S.kp == 128 ? ", 3>" : ", 2>");
     case KT_SOLVE_TQ: return "solve_tq_kernel<" + kp + ", false>";
+    case KT_SOLVE_TQ_MULTI2: return "solve_tq_multi_kernel<" + kp + ", 2>";
+    case KT_SOLVE_TQ_MULTI4: return "solve_tq_multi_kernel<" + kp + ", 4>";
+    case KT_SOLVE_TQ_MULTI8: return "solve_tq_multi_kernel<" + kp + ", 8>";
     case KT_SOLVE_TQ_BIG: return "solve_tq_big_kernel<" + kp + ", false>";
     case KT_SOLVE_JACOBI: return "solve_kernel<" + kp + ", false>";
     case KT_TUNE_Q: return "tune_q_kernel";
@@ -980,10 +983,11 @@ SolveConsts solve_consts(float inflat, int use_rtpp, float rtpp_a, int use_rtps,
 //   per batch       search_batch (S.sstream) -> solve_batch_path (S.stream), with the host
 //                   slab's var piped in and out around it (S.h2d / S.d2h)        (:209-240)
 //   finish_call     info reduction, tune_q (:253-278), write-back, statistics
-// cwbl_analyze_var is a call of one variable; the record path of cwbl_analyze_vars is a group
-// call: nvar variables that share everything but var and the epilogue's flags, so the trees,
-// the batches, the searches and the assembly are variable 0's and only the solve
-// (solve_tq40_multi_kernel), tune_q and the host slab's var see every variable.
+// cwbl_analyze_var is a call of one variable; cwbl_analyze_vars on the record path and on the
+// one-wavefront path is a group call: nvar variables that share everything but var and the
+// epilogue's flags, so the trees, the batches, the searches and the assembly are variable 0's
+// and only the solve (solve_tq40_multi_kernel, solve_tq_multi_kernel), tune_q and the host
+// slab's var see every variable.
 struct VarCall {
   const cwbl_var_params *vp = nullptr;  // [nvar]
   const cwbl_slab *sl = nullptr;        // [nvar]
@@ -1023,6 +1027,8 @@ struct VarCall {
 };
 
 bool record_path() { return S.tq4 && S.kp == kTq4KP && !S.jacobi; }
+// one wavefront per point with the default solver: solve_tq_kernel, solve_tq_multi_kernel
+bool wave_path() { return !record_path() && S.kp <= kMaxWaveKP && !S.jacobi; }
 
 void make_record_key(RecordKey &key, const cwbl_var_params *vp, const cwbl_slab *sl) {
   std::memset(&key, 0, sizeof key);
@@ -1464,8 +1470,8 @@ long long sub_batch(int nb, long long cap) {
 //                solve_tq40_multi_kernel for a group call
 //   k = 65..128  hand-off path: 256-thread kernel (assembly + first steps) -> record ->
 //                solve_tqb_tail_kernel; CWBL_OPT_BIG_PATH = 0: one 256-thread kernel
-//   otherwise    one wavefront per point: solve_tq_kernel; CWBL_OPT_SOLVER = 1: the Jacobi
-//                eigensolver kernel (k <= 64)
+//   otherwise    one wavefront per point: solve_tq_kernel, or solve_tq_multi_kernel for a
+//                group call; CWBL_OPT_SOLVER = 1: the Jacobi eigensolver kernel (k <= 64)
 // b2 / dn: the events around the batch's solve (the record path times its kernel pair
 // between them).  crec (record path): the batch's region of the record cache, which a fill
 // assembles into and a hit (no lists, no assembly) solves from; null: S.wsa.
@@ -1555,6 +1561,11 @@ int solve_batch_path(VarCall &v, long long g0, int nb, const int *ncnt, const in
   } else if (S.jacobi) {
     HIPCHK(launch_solve_neighbors(S.stream, S.kp, dtrees, c, sd, g0, nb, ncnt, nidx, infob));
     HIPCHK(kt_end(S.stream, kt, KT_SOLVE_JACOBI, nb));
+  } else if (v.group) {
+    HIPCHK(launch_solve_tq_multi(S.stream, S.kp, dtrees, c, sd, v.tv, g0, nb, ncnt, nidx, infob));
+    const int nv = group_var_class(v.nvar);
+    HIPCHK(kt_end(S.stream, kt, nv == 2 ? KT_SOLVE_TQ_MULTI2 : nv == 4 ? KT_SOLVE_TQ_MULTI4
+                                                                      : KT_SOLVE_TQ_MULTI8, nb));
   } else {
     HIPCHK(launch_solve_tq(S.stream, S.kp, false, dtrees, c, sd, g0, nb, ncnt, nidx, nullptr,
                            nullptr, nullptr, nullptr, nullptr, infob));
@@ -1939,7 +1950,7 @@ static int begin_call(const cwbl_slab *sl) {
   return CWBL_OK;
 }
 
-// The driver of cwbl_analyze_var and of the record path of cwbl_analyze_vars (v.vp, v.sl, and
+// The driver of cwbl_analyze_var and of the group calls of cwbl_analyze_vars (v.vp, v.sl, and
 // for a group v.nvar, v.group and the flags of v.tv are the caller's; the arguments are
 // checked).  A group call runs with record reuse off: the cache is not read, filled or
 // invalidated.
@@ -2138,9 +2149,9 @@ int cwbl_analyze_vars(int nvar, const cwbl_var_params *vp, const cwbl_slab *slab
   if (int rc = require_device()) return rc;
   if (!S.have_obs) return fail(CWBL_ERR_STATE, "cwbl_set_obs has not been called");
   if (int rc = check_group(nvar, vp, slabs)) return rc;
-  if (record_path()) {
-    // the fused path: per search batch and record sub-batch one search, one assembly and one
-    // solve_tq40_multi_kernel over all variables
+  if (record_path() || (wave_path() && nvar > 1)) {
+    // the fused paths: per search batch (and record sub-batch) one search, one assembly and one
+    // solve_tq40_multi_kernel, or one solve_tq_multi_kernel, over all variables
     VarCall v;
     v.vp = vp;
     v.sl = slabs;
@@ -2155,7 +2166,8 @@ int cwbl_analyze_vars(int nvar, const cwbl_var_params *vp, const cwbl_slab *slab
     }
     return analyze_call(v, stats);
   }
-  // every other path: the variables one after another through cwbl_analyze_var; the
+  // every other path (k > 64, CWBL_OPT_SOLVER = 1) and a one-wavefront group of one: the
+  // variables one after another through cwbl_analyze_var; the
   // counters are the first variable's (they do not depend on the variable), the times summed
   const auto t_start = std::chrono::steady_clock::now();
   cwbl_stats st;

@@ -274,6 +274,16 @@ hipError_t launch_solve_tq40_multi(hipStream_t s, int kp, SolveConsts c, SlabDev
                                    const Tq40Vars &vars, long long g0, int npts, double *ws,
                                    int2 *info);
 
+// The group call of the one-wavefront path (k <= 16, 41..64, and 17..40 without the record
+// split): solve_tq_multi_kernel<KP, NV> (cwbl_tq_multi.hip) is solve_tq_kernel<KP, false> with
+// the x' of up to NV variables carried through one tridiagonalisation.  NV is the class of
+// the group's size (unused slots carry zeros); the same data contract as launch_solve_tq's
+// slab mode, with the variables' table in place of slab.var.  nvar >= 2.
+constexpr int group_var_class(int nvar) { return nvar <= 2 ? 2 : nvar <= 4 ? 4 : 8; }
+hipError_t launch_solve_tq_multi(hipStream_t s, int kp, const TreeDesc *trees, SolveConsts c,
+                                 SlabDev slab, const Tq40Vars &vars, long long g0, int npts,
+                                 const int *nbr_cnt, const int *nbr_idx, int2 *info);
+
 // Split form of the KP = 128 slab path (configs[3]: k = 97..128).  solve_tq_big_kernel<128,
 // false, kBigJ0> assembles A and runs the first kBigJ0 Householder steps (4x4 register
 // blocks over 256 threads, one point per workgroup), then hands the trailing

@@ -377,7 +377,11 @@ class Core:
     def analyze_vars(self, vps, slabs):
         """cwbl_analyze_vars: up to MAX_GROUP_VARS variables that share a localisation (equal
         multi_infl and type parameters, one grid: the same x, y, alt arrays) in one call.
-        vps, slabs: sequences of VarParams / Slab of equal length; returns the call's Stats."""
+        Fused (one search, one assembly and one tridiagonalisation per point for the whole
+        group) on the k = 17..40 record path and, for two or more variables, on the
+        one-wavefront path (k <= 16, k = 41..64, k = 17..40 with split40 = 0); with k > 64 or
+        solver = 1 the variables run one after another.  Bit-identical to analyze_var either
+        way.  vps, slabs: sequences of VarParams / Slab of equal length; returns the call's Stats."""
         vps, slabs = list(vps), list(slabs)
         if len(vps) != len(slabs):
             raise ValueError("analyze_vars: as many VarParams as Slabs")

@@ -212,13 +212,16 @@ int         cwbl_analyze_var(const cwbl_var_params *vp, const cwbl_slab *slab,
 
 /* cwbl_analyze_var for up to CWBL_MAX_GROUP_VARS variables that share a localisation, in one
  * call.  The LETKF weights of a grid point depend on the obs, the localisation, multi_infl and
- * the point's coordinates, not on the analysed variable; on the k = 17..40 record path the
- * call searches, assembles and tridiagonalises once per point and applies the factor to every
- * variable (solve_tq40_multi_kernel).  Each variable's result and the counters are those of
+ * the point's coordinates, not on the analysed variable.  Two paths fuse the group: on the
+ * k = 17..40 record path the call searches, assembles and tridiagonalises once per point and
+ * replays the factor on every variable (solve_tq40_multi_kernel); on the one-wavefront path
+ * (k <= 16, k = 41..64, and k = 17..40 under CWBL_OPT_SPLIT40 = 0) a group of two or more
+ * searches, assembles and tridiagonalises once per point with every variable carried through
+ * the steps (solve_tq_multi_kernel).  Each variable's result and the counters are those of
  * cwbl_analyze_var on the same inputs, bit for bit.  It keeps no cache and neither reads,
  * fills nor invalidates the record cache (CWBL_OPT_RECORD_REUSE), so it saves the same work
- * at any grid size and memory budget.  On every other path (k <= 16, k > 40,
- * CWBL_OPT_SOLVER = 1, CWBL_OPT_SPLIT40 = 0) the variables run one after another through
+ * at any grid size and memory budget.  Elsewhere (k > 64, CWBL_OPT_SOLVER = 1, and a group of
+ * one on the one-wavefront path) the variables run one after another through
  * cwbl_analyze_var's code.
  *
  * Group rule (checked before any device work; a violation returns CWBL_ERR_ARG and the message
