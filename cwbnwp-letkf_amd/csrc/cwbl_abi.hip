@@ -224,7 +224,9 @@ struct TreeBufs {
 enum KernelId {
   KT_SEARCH_BINNED, KT_SEARCH_FLAGGED, KT_SEARCH_TREE, KT_ASSEMBLE_RECORD, KT_SOLVE_TQ40,
   KT_SOLVE_TQ40_MULTI, KT_SOLVE_TQ_MULTI2, KT_SOLVE_TQ_MULTI4, KT_SOLVE_TQ_MULTI8,
-  KT_BIG_HANDOFF, KT_TQB_TAIL, KT_SOLVE_TQ, KT_SOLVE_TQ_BIG, KT_SOLVE_JACOBI, KT_TUNE_Q,
+  KT_BIG_HANDOFF, KT_TQB_TAIL, KT_BIG_HANDOFF_MULTI2, KT_BIG_HANDOFF_MULTI4,
+  KT_BIG_HANDOFF_MULTI8, KT_TQB_TAIL_MULTI2, KT_TQB_TAIL_MULTI4, KT_TQB_TAIL_MULTI8,
+  KT_SOLVE_TQ, KT_SOLVE_TQ_BIG, KT_SOLVE_JACOBI, KT_TUNE_Q,
   KT_COUNT
 };
 struct KTime { long long launches = 0, points = 0; double ms = 0.0; };
@@ -486,6 +488,18 @@ std::string kernel_name(int id) {
     case KT_TQB_TAIL:
       return "solve_tqb_tail_kernel<" + kp + ", " + std::to_string(big_split_j0(S.kp)) +
              (S.kp == 128 ? ", 3>" : ", 2>");
+    case KT_BIG_HANDOFF_MULTI2:
+    case KT_BIG_HANDOFF_MULTI4:
+    case KT_BIG_HANDOFF_MULTI8: {
+      const std::string nv = std::to_string(2 << (id - KT_BIG_HANDOFF_MULTI2));
+      return (S.kp == 128 ? "solve_tq_rows_multi_kernel<128, 64, "
+                          : "solve_tq_big_multi_kernel<96, 32, ") + nv + ">";
+    }
+    case KT_TQB_TAIL_MULTI2:
+    case KT_TQB_TAIL_MULTI4:
+    case KT_TQB_TAIL_MULTI8:
+      return "solve_tqb_tail_multi_kernel<" + kp + ", " + std::to_string(big_split_j0(S.kp)) +
+             ", " + std::to_string(2 << (id - KT_TQB_TAIL_MULTI2)) + ">";
     case KT_SOLVE_TQ: return "solve_tq_kernel<" + kp + ", false>";
     case KT_SOLVE_TQ_MULTI2: return "solve_tq_multi_kernel<" + kp + ", 2>";
     case KT_SOLVE_TQ_MULTI4: return "solve_tq_multi_kernel<" + kp + ", 4>";
@@ -1029,6 +1043,12 @@ struct VarCall {
 bool record_path() { return S.tq4 && S.kp == kTq4KP && !S.jacobi; }
 // one wavefront per point with the default solver: solve_tq_kernel, solve_tq_multi_kernel
 bool wave_path() { return !record_path() && S.kp <= kMaxWaveKP && !S.jacobi; }
+// the hand-off path (k = 65..128 under CWBL_OPT_BIG_PATH = 1: a 256-thread kernel for the
+// assembly and the first steps, a record, the one-wavefront tail kernel) is what a call runs
+// (CWBL_OPT_SOLVER does not reach k > 64)
+bool handoff_path() {
+  return (S.kp == 96 || S.kp == kBigSplitKP) && S.big_split && S.k > big_split_j0(S.kp) + 2;
+}
 
 void make_record_key(RecordKey &key, const cwbl_var_params *vp, const cwbl_slab *sl) {
   std::memset(&key, 0, sizeof key);
@@ -1469,7 +1489,8 @@ long long sub_batch(int nb, long long cap) {
 //   k = 17..40   record path: assemble_record_kernel -> record -> solve_tq40_kernel, or
 //                solve_tq40_multi_kernel for a group call
 //   k = 65..128  hand-off path: 256-thread kernel (assembly + first steps) -> record ->
-//                solve_tqb_tail_kernel; CWBL_OPT_BIG_PATH = 0: one 256-thread kernel
+//                solve_tqb_tail_kernel, or the group forms of the two for a group call;
+//                CWBL_OPT_BIG_PATH = 0: one 256-thread kernel
 //   otherwise    one wavefront per point: solve_tq_kernel, or solve_tq_multi_kernel for a
 //                group call; CWBL_OPT_SOLVER = 1: the Jacobi eigensolver kernel (k <= 64)
 // b2 / dn: the events around the batch's solve (the record path times its kernel pair
@@ -1483,8 +1504,7 @@ int solve_batch_path(VarCall &v, long long g0, int nb, const int *ncnt, const in
   const SlabDev &sd = v.sd;
   const int nt = v.nt, list_cap = v.list_cap;
   int kt;
-  const bool handoff = (S.kp == 96 || S.kp == kBigSplitKP) && S.big_split &&
-                       S.k > big_split_j0(S.kp) + 2;
+  const bool handoff = handoff_path();
   if (record_path()) {
     // (Bs <= 2^19: the solve addresses a sub-batch's records with 32-bit byte offsets)
     const long long cap = std::min<long long>(S.tq4_sub > 0 ? S.tq4_sub : nb, 1 << 19);
@@ -1534,8 +1554,10 @@ int solve_batch_path(VarCall &v, long long g0, int nb, const int *ncnt, const in
     // sub-batch, outside workspace_bytes); the sub-batch is also bounded by the hand-off
     // budget (cwbl_init: workspace_bytes when the caller gave one, else 13 GB or 40% of the
     // free device memory)
-    const size_t rec_bytes = (size_t)8 * (S.kp == 96 ? BigHandoff<96, 32>::WORDS
-                                                     : BigHandoff<kBigSplitKP, kBigJ0>::WORDS);
+    // (a group's record carries the further variables' Q^T x': BigHandoffMulti)
+    const int nv = v.group ? group_var_class(v.nvar) : 1;
+    const size_t rec_bytes = 8 * big_handoff_words(S.kp, nv);
+    const int ci = nv == 2 ? 0 : nv == 4 ? 1 : 2;  // the group kernels' KernelId offset
     const long long fit = std::max<long long>(
         kListLanes, (long long)(S.handoff_budget / rec_bytes) / kListLanes * kListLanes);
     const long long Bs = sub_batch(nb, std::min<long long>(S.big_sub, fit));
@@ -1543,6 +1565,17 @@ int solve_batch_path(VarCall &v, long long g0, int nb, const int *ncnt, const in
     for (long long s0 = 0; s0 < nb; s0 += Bs) {
       const int ns = (int)std::min<long long>(Bs, nb - s0);
       HIPCHK(kt_begin(S.stream, &kt));
+      if (v.group) {
+        HIPCHK(launch_big_handoff_multi(S.stream, S.kp, dtrees, c, sd, v.tv, g0 + s0, ns,
+                                        ncnt + s0 * nt, nidx + s0 * list_cap, infob + s0,
+                                        S.wsa.as<double>()));
+        HIPCHK(kt_end(S.stream, kt, KT_BIG_HANDOFF_MULTI2 + ci, ns));
+        HIPCHK(kt_begin(S.stream, &kt));
+        HIPCHK(launch_solve_tqb_tail_multi(S.stream, S.kp, c, sd, v.tv, g0 + s0, ns,
+                                           S.wsa.as<double>(), infob + s0));
+        HIPCHK(kt_end(S.stream, kt, KT_TQB_TAIL_MULTI2 + ci, ns));
+        continue;
+      }
       HIPCHK(launch_big_handoff(S.stream, S.kp, dtrees, c, sd, g0 + s0, ns, ncnt + s0 * nt,
                                 nidx + s0 * list_cap, infob + s0, S.wsa.as<double>()));
       HIPCHK(kt_end(S.stream, kt, KT_BIG_HANDOFF, ns));
@@ -2149,9 +2182,11 @@ int cwbl_analyze_vars(int nvar, const cwbl_var_params *vp, const cwbl_slab *slab
   if (int rc = require_device()) return rc;
   if (!S.have_obs) return fail(CWBL_ERR_STATE, "cwbl_set_obs has not been called");
   if (int rc = check_group(nvar, vp, slabs)) return rc;
-  if (record_path() || (wave_path() && nvar > 1)) {
+  if (record_path() || ((wave_path() || (handoff_path() && !S.jacobi)) && nvar > 1)) {
     // the fused paths: per search batch (and record sub-batch) one search, one assembly and one
-    // solve_tq40_multi_kernel, or one solve_tq_multi_kernel, over all variables
+    // solve_tq40_multi_kernel, or one solve_tq_multi_kernel, or one hand-off kernel pair
+    // (solve_tq_rows_multi_kernel / solve_tq_big_multi_kernel, solve_tqb_tail_multi_kernel),
+    // over all variables
     VarCall v;
     v.vp = vp;
     v.sl = slabs;
@@ -2166,8 +2201,8 @@ int cwbl_analyze_vars(int nvar, const cwbl_var_params *vp, const cwbl_slab *slab
     }
     return analyze_call(v, stats);
   }
-  // every other path (k > 64, CWBL_OPT_SOLVER = 1) and a one-wavefront group of one: the
-  // variables one after another through cwbl_analyze_var; the
+  // every other path (CWBL_OPT_SOLVER = 1, k > 64 under CWBL_OPT_BIG_PATH = 0) and a group of
+  // one outside the record path: the variables one after another through cwbl_analyze_var; the
   // counters are the first variable's (they do not depend on the variable), the times summed
   const auto t_start = std::chrono::steady_clock::now();
   cwbl_stats st;

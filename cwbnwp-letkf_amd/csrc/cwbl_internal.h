@@ -318,6 +318,39 @@ hipError_t launch_rows_handoff(hipStream_t s, const TreeDesc *trees, SolveConsts
 hipError_t launch_solve_tqb_tail(hipStream_t s, int kp, SolveConsts c, SlabDev slab,
                                  long long g0, int npts, double *ws, int2 *info);
 
+// The group call of the hand-off path (k = 65..128, cwbl_analyze_vars with two or more
+// variables): solve_tq_rows_multi_kernel<128, 64, NV> (cwbl_tq_rows_multi.hip) and
+// solve_tq_big_multi_kernel<96, 32, NV> (cwbl_tq_big_multi.hip) are the hand-off kernels with
+// the x' of up to NV variables carried through the steps, solve_tqb_tail_multi_kernel<KP, J0,
+// NV> (cwbl_tq_tail_multi.hip) the tail kernel likewise, which then solves variable by
+// variable.  The record is BigHandoff's with the further variables' Q^T x' appended, so that
+// every word the single kernels address keeps its place.
+template <int KP, int J0, int NV>
+struct BigHandoffMulti : BigHandoff<KP, J0> {
+  using Base = BigHandoff<KP, J0>;
+  static constexpr int U2X = Base::WORDS;  // Q_J0^T x' of variables 1 .. NV-1 (KP each)
+  static constexpr int WORDS = U2X + (NV - 1) * KP;
+  // Q_J0^T x' of variable i
+  __host__ __device__ static constexpr int u2(int i) { return i == 0 ? Base::U2 : U2X + (i - 1) * KP; }
+};
+// fp64 words of a point's record on the hand-off path: a single call's (nv <= 1) or a group's
+// of class nv (group_var_class)
+constexpr size_t big_handoff_words(int kp, int nv) {
+  return (size_t)(kp == 96 ? BigHandoff<96, 32>::WORDS : BigHandoff<kBigSplitKP, kBigJ0>::WORDS) +
+         (size_t)(nv > 1 ? nv - 1 : 0) * kp;
+}
+hipError_t launch_big_handoff_multi(hipStream_t s, int kp, const TreeDesc *trees, SolveConsts c,
+                                    SlabDev slab, const Tq40Vars &vars, long long g0, int npts,
+                                    const int *nbr_cnt, const int *nbr_idx, int2 *info,
+                                    double *ws);
+hipError_t launch_rows_handoff_multi(hipStream_t s, const TreeDesc *trees, SolveConsts c,
+                                     SlabDev slab, const Tq40Vars &vars, long long g0, int npts,
+                                     const int *nbr_cnt, const int *nbr_idx, int2 *info,
+                                     double *ws);
+hipError_t launch_solve_tqb_tail_multi(hipStream_t s, int kp, SolveConsts c, SlabDev slab,
+                                       const Tq40Vars &vars, long long g0, int npts, double *ws,
+                                       int2 *info);
+
 // KP = 96, 128: one 256-thread workgroup per point (cwbl_tq_big.hip)
 hipError_t launch_solve_tq_big(hipStream_t s, int kp, bool assembled, const TreeDesc *trees,
                                SolveConsts c, SlabDev slab, long long g0, int npts,

@@ -212,17 +212,19 @@ int         cwbl_analyze_var(const cwbl_var_params *vp, const cwbl_slab *slab,
 
 /* cwbl_analyze_var for up to CWBL_MAX_GROUP_VARS variables that share a localisation, in one
  * call.  The LETKF weights of a grid point depend on the obs, the localisation, multi_infl and
- * the point's coordinates, not on the analysed variable.  Two paths fuse the group: on the
+ * the point's coordinates, not on the analysed variable.  Three paths fuse the group: on the
  * k = 17..40 record path the call searches, assembles and tridiagonalises once per point and
  * replays the factor on every variable (solve_tq40_multi_kernel); on the one-wavefront path
  * (k <= 16, k = 41..64, and k = 17..40 under CWBL_OPT_SPLIT40 = 0) a group of two or more
  * searches, assembles and tridiagonalises once per point with every variable carried through
- * the steps (solve_tq_multi_kernel).  Each variable's result and the counters are those of
- * cwbl_analyze_var on the same inputs, bit for bit.  It keeps no cache and neither reads,
- * fills nor invalidates the record cache (CWBL_OPT_RECORD_REUSE), so it saves the same work
- * at any grid size and memory budget.  Elsewhere (k > 64, CWBL_OPT_SOLVER = 1, and a group of
- * one on the one-wavefront path) the variables run one after another through
- * cwbl_analyze_var's code.
+ * the steps (solve_tq_multi_kernel); on the k = 65..128 hand-off path a group of two or more
+ * does the same in the group forms of its kernel pair (solve_tq_big_multi_kernel or
+ * solve_tq_rows_multi_kernel, then solve_tqb_tail_multi_kernel).  Each variable's result and
+ * the counters are those of cwbl_analyze_var on the same inputs, bit for bit.  It keeps no
+ * cache and neither reads, fills nor invalidates the record cache (CWBL_OPT_RECORD_REUSE), so
+ * it saves the same work at any grid size and memory budget.  Elsewhere (CWBL_OPT_SOLVER = 1,
+ * k > 64 under CWBL_OPT_BIG_PATH = 0, and a group of one outside the record path) the
+ * variables run one after another through cwbl_analyze_var's code.
  *
  * Group rule (checked before any device work; a violation returns CWBL_ERR_ARG and the message
  * names the variable index and the field): 1 <= nvar <= CWBL_MAX_GROUP_VARS; every slabs[i]
