@@ -247,3 +247,43 @@ def pair_ensemble(w, err, seed=5):
     # rounding, and RTPS would rescale that rounding by ~1e7 (RTPP keeps alpha xb')
     w.vp.use_rtps = 0
     return w
+
+
+# ---- the tq kernels' quadrature rule of a point, restated -------------------------------------
+# Mirrors of cwbnwp-letkf_amd/csrc/cwbl_internal.h (kQuadLevels, kQuadLevels31, quad_rounds,
+# quad_passes); tests/test_truth_spectra.py pins them against the header's text.
+QUAD_LEVELS = 24
+QUAD_LEVELS_31 = 12
+
+
+def quad_level(ratio):
+    """The level the tq kernels choose for the spectrum bound M/m = ratio: the decade loop of
+    every solve_tq*_kernel (`level = 1; dec = 10; while level < kQuadLevels and dec < ratio`)."""
+    level, dec = 1, 10.0
+    while level < QUAD_LEVELS and dec < ratio:
+        dec *= 10.0
+        level += 1
+    return level
+
+
+def quad_rounds(level):
+    """Rounds of 8 nodes of solve_tq40(_multi)_kernel at a level: R = 2, 3, 4 or 8."""
+    return 2 if level <= 3 else 3 if level <= 5 else 4 if level <= QUAD_LEVELS_31 else 8
+
+
+def quad_passes(level):
+    """Passes of 31 nodes of the one-wavefront and tail kernels at a level: 1 or 2."""
+    return 1 if level <= QUAD_LEVELS_31 else 2
+
+
+def spectrum_ratio(yb, inflat):
+    """M/m = trace(A)/m - (k-1) = 1 + sum(yb^2)/inflat in fp64 (A = inflat I + Yb^T Yb)."""
+    yb8 = np.asarray(yb, np.float64)
+    return 1.0 + float(np.sum(yb8 * yb8)) / float(np.float32(inflat))
+
+
+def near_decade(ratio, rel=1e-9):
+    """True where ratio lies within rel (relative) of a power of ten: there the kernels' fp64
+    trace, summed in another order, may land on the other side of the level boundary."""
+    e = np.round(np.log10(ratio))
+    return abs(ratio - 10.0 ** e) <= rel * 10.0 ** e

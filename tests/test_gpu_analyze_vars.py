@@ -5,8 +5,11 @@ On the k = 17..40 record path the call searches and assembles once per batch and
 solve_tq40_multi_kernel, which tridiagonalises once per point and replays the reflectors on
 every variable's x'.  The replay evaluates the expressions of solve_tq40_kernel, so every
 comparison with the per-variable calls (`seq`: cwbl_analyze_var per variable on a fresh core)
-is exact: np.array_equal on the bit patterns, plus the counters.  Only the oracle comparison
-has a tolerance, the project's path-versus-oracle bar INCR_TOL.
+is exact: np.array_equal on the bit patterns, plus the counters.  Here only the oracle
+comparison has a tolerance, the project's path-versus-oracle bar INCR_TOL, and every input is
+the benign c2 one (levels 1..3, one radar type, Gaussian weights): the wide spectra, the fp64
+truth, non-finite variables and the reference's mixed-obs cases are in
+tests/test_gpu_analyze_vars_spectra.py and tests/test_gpu_analyze_vars_golden.py.
 
 Workload: synth c2 at scale 0.1 (30 x 30 x 50 = 45 000 points, k = 40, 225 obs) in search
 batches of 1024 points and record sub-batches of 512: 44 batches of two sub-batches, without
@@ -60,19 +63,23 @@ class Lib:
     """One library state with the workload's obs set and its coordinates on the device (or,
     host=True, in pageable numpy arrays): one set of x, y, alt arrays for every slab."""
 
-    def __init__(self, w, opts=None, host=False, reuse_default=False):
+    def __init__(self, w, opts=None, host=False, reuse_default=False, weight_function=0,
+                 norain_value=-5.0, obs_set=None):
+        """obs_set: a built cwbl_obs_set instead of the workload's one radar type."""
         options = dict(OPTS)
         if reuse_default:
             del options["record_reuse"]
         options.update(opts or {})
         self.w, self.host = w, host
-        self.c = abi.Core(w.k, device=0, options=options)
-        self.c.set_obs(abi.ObsSetBuilder().add_radar(w.radar_type, w.obs_xyz, w.obs, w.hdxb).build())
+        self.c = abi.Core(w.k, device=0, weight_function=weight_function,
+                          norain_value=norain_value, options=options)
+        self.c.set_obs(obs_set if obs_set is not None else abi.ObsSetBuilder().add_radar(
+            w.radar_type, w.obs_xyz, w.obs, w.hdxb).build())
         self.x, self.y, self.alt = (a.copy() if host else to_dev(a) for a in (w.x, w.y, w.alt))
 
-    def slab(self, v, ix_lim=None, alt=None):
+    def slab(self, v, ix_lim=None, alt=None, iy_lim=None):
         return abi.make_slab(self.x, self.y, self.alt if alt is None else alt, v, ix_lim=ix_lim,
-                             memory=abi.MEM_HOST if self.host else abi.MEM_DEVICE)
+                             iy_lim=iy_lim, memory=abi.MEM_HOST if self.host else abi.MEM_DEVICE)
 
     def buffers(self, vars_):
         if self.host:
@@ -85,33 +92,33 @@ class Lib:
     def fetch(b):
         return b if isinstance(b, np.ndarray) else b.cpu().numpy()
 
-    def one(self, var, vp, ix_lim=None):
+    def one(self, var, vp, ix_lim=None, iy_lim=None):
         """cwbl_analyze_var on a copy of var: (analysis, counters)."""
         b, = self.buffers([var])
-        st = self.c.analyze_var(vp, self.slab(b, ix_lim))
+        st = self.c.analyze_var(vp, self.slab(b, ix_lim, iy_lim=iy_lim))
         return self.fetch(b), counters(st)
 
-    def group(self, vars_, vps, ix_lim=None):
+    def group(self, vars_, vps, ix_lim=None, iy_lim=None):
         """cwbl_analyze_vars on copies of vars_: ([analysis], counters)."""
         bufs = self.buffers(vars_)
-        st = self.c.analyze_vars(vps, [self.slab(b, ix_lim) for b in bufs])
+        st = self.c.analyze_vars(vps, [self.slab(b, ix_lim, iy_lim=iy_lim) for b in bufs])
         return [self.fetch(b) for b in bufs], counters(st)
 
     def close(self):
         self.c.finalize()
 
 
-def seq(w, vars_, vps, opts=None, ix_lim=None):
+def seq(w, vars_, vps, opts=None, ix_lim=None, **core):
     """cwbl_analyze_var per variable on a fresh core: [(analysis, counters)]."""
-    lib = Lib(w, opts)
+    lib = Lib(w, opts, **core)
     try:
         return [lib.one(v, vp, ix_lim) for v, vp in zip(vars_, vps)]
     finally:
         lib.close()
 
 
-def group(w, vars_, vps, opts=None, ix_lim=None, host=False):
-    lib = Lib(w, opts, host=host)
+def group(w, vars_, vps, opts=None, ix_lim=None, host=False, **core):
+    lib = Lib(w, opts, host=host, **core)
     try:
         return lib.group(vars_, vps, ix_lim)
     finally:

@@ -4,8 +4,11 @@ and one solve_tqb_tail_multi_kernel per sub-batch for the whole group.  The kern
 and tridiagonalise once per point and carry every variable's x' through the steps with the
 single kernels' expressions, so every comparison with the per-variable calls (`seq`:
 cwbl_analyze_var per variable on a fresh core) is exact: np.array_equal on the bit patterns,
-plus the counters.  Only the oracle comparison has a tolerance, the project's
-path-versus-oracle bar INCR_TOL.
+plus the counters.  Here only the oracle comparison has a tolerance, the project's
+path-versus-oracle bar INCR_TOL, and every input is the benign c2 one (levels 1..3, a single
+quadrature pass): the second pass, the fp64 truth and non-finite variables are in
+tests/test_gpu_analyze_vars_spectra.py, two obs types, Gaspari-Cohn weights and truncated
+lists in tests/test_gpu_analyze_vars_big_mixed.py.
 
 Workloads: synth c2 on 12 x 12 x 5 = 720 points in search batches of at most 256 points (three
 batches per call), with 400 obs (every point has p above every k: full-rank Yb Yb^T), with

@@ -3,8 +3,11 @@ k = 17..40 with split40 = 0): one search and one solve_tq_multi_kernel per batch
 group.  The kernel tridiagonalises once per point and carries every variable's x' through the
 steps with solve_tq_kernel's expressions, so every comparison with the per-variable calls
 (`seq`: cwbl_analyze_var per variable on a fresh core) is exact: np.array_equal on the bit
-patterns, plus the counters.  Only the oracle comparison has a tolerance, the project's
-path-versus-oracle bar INCR_TOL.
+patterns, plus the counters.  Here only the oracle comparison has a tolerance, the project's
+path-versus-oracle bar INCR_TOL, and every input is the benign c2 one (levels 1..3, a single
+quadrature pass): the second pass, the fp64 truth, non-finite variables and the reference's
+mixed-obs cases are in tests/test_gpu_analyze_vars_spectra.py and
+tests/test_gpu_analyze_vars_golden.py.
 
 Workload: synth c2 on 12 x 12 x 5 = 720 points with 120 obs, in search batches of at most 256
 points, so a call runs three batches (the search of one overlaps the solve of the one before).

@@ -30,14 +30,13 @@ def test_eigen_direct_equals_the_oracle_in_the_ordinary_regime():
         assert increment_rel_rms(xa, ref[:, kz, j, i], w.var[:, kz, j, i]) <= 1e-12
 
 
-@pytest.mark.parametrize("k", [16, 32])
-def test_eigen_direct_equals_50_digits_with_tiny_obs_errors(k):
-    mp = pytest.importorskip("mpmath")
-    err = 2.0 ** -20
-    w = pair_ensemble(synth.make("c2", seed=13, scale=0.06, nz=4, k=k), err)
+def _equals_50_digits(mp, w, err, points):
+    """eigen-direct before the fp32 epilogue against 50-digit arithmetic at the given points
+    of a pair-ensemble workload whose spectrum bound exceeds 1e12."""
+    k = w.k
     infl = inflat_of(k, w.vp.multi_infl)
     mp.mp.dps = 50
-    for kz, j, i in POINTS[:2]:
+    for kz, j, i in points:
         yo, yb = radar_point_columns(w, kz, j, i, err)
         p = len(yo)
         # eigen-direct before the fp32 epilogue (RTPP/RTPS off, analysis in fp64 kept)
@@ -67,3 +66,23 @@ def test_eigen_direct_equals_50_digits_with_tiny_obs_errors(k):
         hp = np.array([float(mp.mpf(xm) + dm + mp.sqrt(k - 1) * wx[m]) for m in range(k)])
         assert np.max(np.abs(pre - hp)) <= 1e-13, np.max(np.abs(pre - hp))
         assert float(mp.fsum(A[a, a] for a in range(k))) / float(infl) - (k - 1) > 1e12
+
+
+@pytest.mark.parametrize("k", [16, 32])
+def test_eigen_direct_equals_50_digits_with_tiny_obs_errors(k):
+    mp = pytest.importorskip("mpmath")
+    err = 2.0 ** -20
+    w = pair_ensemble(synth.make("c2", seed=13, scale=0.06, nz=4, k=k), err)
+    _equals_50_digits(mp, w, err, POINTS[:2])
+
+
+@pytest.mark.parametrize("k", [64, 96, 128])
+def test_eigen_direct_equals_50_digits_on_the_group_spectra_workloads(k):
+    """One point of the 2^-19 workload of tests/test_gpu_analyze_vars_spectra.py at the larger
+    ensemble sizes (a point takes about 4 s at k = 64, 15 s at 96, 35 s at 128 in mpmath); the
+    other points and cases of those sizes rest on the reversed-column floor
+    (tests/test_truth_spectra.py)."""
+    mp = pytest.importorskip("mpmath")
+    import spectra_cases as sc
+    c, = [c for c in sc.CASES if c.k == k and c.e == -19]
+    _equals_50_digits(mp, sc.workload(c), 2.0 ** c.e, [(2, 6, 5)])
