@@ -223,7 +223,7 @@ struct TreeBufs {
 
 enum KernelId {
   KT_SEARCH_BINNED, KT_SEARCH_FLAGGED, KT_SEARCH_TREE, KT_ASSEMBLE_RECORD, KT_SOLVE_TQ40,
-  KT_SOLVE_TQ40_MULTI, KT_SOLVE_TQ_MULTI2, KT_SOLVE_TQ_MULTI4, KT_SOLVE_TQ_MULTI8,
+  KT_SOLVE_TQ40_MULTI, KT_SOLVE_TQ40_COLUMN, KT_SOLVE_TQ_MULTI2, KT_SOLVE_TQ_MULTI4, KT_SOLVE_TQ_MULTI8,
   KT_BIG_HANDOFF, KT_TQB_TAIL, KT_BIG_HANDOFF_MULTI2, KT_BIG_HANDOFF_MULTI4,
   KT_BIG_HANDOFF_MULTI8, KT_TQB_TAIL_MULTI2, KT_TQB_TAIL_MULTI4, KT_TQB_TAIL_MULTI8,
   KT_SOLVE_TQ, KT_SOLVE_TQ_BIG, KT_SOLVE_JACOBI, KT_TUNE_Q,
@@ -331,6 +331,9 @@ struct State {
   size_t handoff_budget = 0;                          // bytes for the k > 64 hand-off records
   unsigned long long gen = 0;     // bumped by cwbl_init, cwbl_set_obs and cwbl_set_option
   size_t reuse_budget = 0;        // CWBL_OPT_RECORD_REUSE in bytes (0: no reuse)
+  int column_share = 0;           // CWBL_OPT_COLUMN_SHARE: 0 off, 1 column kernel, 2 chunks only
+  int column_levels = 0;          // CWBL_OPT_COLUMN_LEVELS: levels per wave (0: automatic)
+  int ncu = 0;                    // compute units of the device (automatic level split)
   RecordCache cache;
   // pageable host slabs: each batch's var columns go through page-locked bounce slots (two
   // in, two out), filled and drained by a few host threads while the GPU runs other batches
@@ -481,6 +484,7 @@ std::string kernel_name(int id) {
     case KT_ASSEMBLE_RECORD: return "assemble_record_kernel<" + std::to_string(kRecordWaves) + ">";
     case KT_SOLVE_TQ40: return "solve_tq40_kernel<" + kp + ", 0>";
     case KT_SOLVE_TQ40_MULTI: return "solve_tq40_multi_kernel<" + kp + ">";
+    case KT_SOLVE_TQ40_COLUMN: return "solve_tq40_column_kernel<" + kp + ">";
     case KT_BIG_HANDOFF:
       return S.kp == 128 ? "solve_tq_rows_kernel<128, 64>"
                          : "solve_tq_big_kernel<" + kp + ", false, " +
@@ -589,6 +593,7 @@ int bin_div_for(const HostTree &t, int dim) {
 }
 
 cwbl_reuse_info_t R;  // cwbl_reuse_info: what the current cwbl_analyze_var reused
+cwbl_column_info_t CI;  // cwbl_column_info: what it shared per column (CWBL_OPT_COLUMN_SHARE)
 
 // ---- cwbl_prep_info: what the current cwbl_analyze_var spends on its search index -----------
 cwbl_prep_info_t P;
@@ -1001,7 +1006,9 @@ SolveConsts solve_consts(float inflat, int use_rtpp, float rtpp_a, int use_rtps,
 // one-wavefront path is a group call: nvar variables that share everything but var and the
 // epilogue's flags, so the trees, the batches, the searches and the assembly are variable 0's
 // and only the solve (solve_tq40_multi_kernel, solve_tq_multi_kernel), tune_q and the host
-// slab's var see every variable.
+// slab's var see every variable.  A column-shared call (CWBL_OPT_COLUMN_SHARE: one variable
+// whose trees are all 2-D) runs the same stages over the column view of its slab, and its
+// solves (solve_batch_column) cover every level of a batch's columns.
 struct VarCall {
   const cwbl_var_params *vp = nullptr;  // [nvar]
   const cwbl_slab *sl = nullptr;        // [nvar]
@@ -1038,6 +1045,14 @@ struct VarCall {
   int reuse = 0;
   long long ncached = 0;
   bool full_hit = false;
+  // CWBL_OPT_COLUMN_SHARE (1 or 2 when the call is shared, else 0): sd is the column view of
+  // the slab (nz = 1; L stays the member stride nx ny nz) and npts its ncol = ix_lim iy_lim
+  // points, so the plan, the searches, the lists, the assembly and the info windows are per
+  // column; `full` is the slab itself, nlev its nz.  lev: levels a solve launch of
+  // solve_batch_path covers (its kernel-timing points are points x lev).
+  int colshare = 0, nlev = 1, lev = 1;
+  long long ncol = 0;
+  SlabDev full{};
 };
 
 bool record_path() { return S.tq4 && S.kp == kTq4KP && !S.jacobi; }
@@ -1196,14 +1211,16 @@ int stage_slab(VarCall &v) {
   v.bvar = (size_t)v.L * S.k * 4;
   v.host = sl->memory != CWBL_MEM_DEVICE;
   // (a group's host slabs move whole, from wherever they lie: not piped, page-locked or bounced)
-  v.piped = !v.group && v.host && sl->ix_lim == sl->nx && sl->iy_lim == sl->ny;
+  // (so do a column-shared call's: its batches are columns, not contiguous runs of var)
+  const bool whole = v.group || v.colshare;
+  v.piped = !whole && v.host && sl->ix_lim == sl->nx && sl->iy_lim == sl->ny;
   v.piped_back = v.piped && !v.vp->tune_q;  // tune_q touches the whole slab afterwards
   // pageable var (a Fortran host's ordinary arrays): copies from pageable memory are staged by
   // the runtime and do not overlap.  It is page-locked in place for the call (r4, C2 from
   // pageable numpy arrays: 58.7 M pts/s, against 58.2 M page-locked and 50.8 M through the
   // bounce slots, whose host copies stall the pipeline); the slots remain the fallback when
   // the registration fails (and CWBL_OPT_PAGEABLE = 1 forces them)
-  v.bounce = !v.group && v.host && v.bvar > 0 && !host_pinned(sl->var);
+  v.bounce = !whole && v.host && v.bvar > 0 && !host_pinned(sl->var);
   if (v.bounce && S.pageable_register) {
     if (hipHostRegister(sl->var, v.bvar, hipHostRegisterDefault) == hipSuccess) {
       v.registered = true;
@@ -1569,11 +1586,11 @@ int solve_batch_path(VarCall &v, long long g0, int nb, const int *ncnt, const in
         HIPCHK(launch_big_handoff_multi(S.stream, S.kp, dtrees, c, sd, v.tv, g0 + s0, ns,
                                         ncnt + s0 * nt, nidx + s0 * list_cap, infob + s0,
                                         S.wsa.as<double>()));
-        HIPCHK(kt_end(S.stream, kt, KT_BIG_HANDOFF_MULTI2 + ci, ns));
+        HIPCHK(kt_end(S.stream, kt, KT_BIG_HANDOFF_MULTI2 + ci, (long long)ns * v.lev));
         HIPCHK(kt_begin(S.stream, &kt));
         HIPCHK(launch_solve_tqb_tail_multi(S.stream, S.kp, c, sd, v.tv, g0 + s0, ns,
                                            S.wsa.as<double>(), infob + s0));
-        HIPCHK(kt_end(S.stream, kt, KT_TQB_TAIL_MULTI2 + ci, ns));
+        HIPCHK(kt_end(S.stream, kt, KT_TQB_TAIL_MULTI2 + ci, (long long)ns * v.lev));
         continue;
       }
       HIPCHK(launch_big_handoff(S.stream, S.kp, dtrees, c, sd, g0 + s0, ns, ncnt + s0 * nt,
@@ -1598,11 +1615,135 @@ int solve_batch_path(VarCall &v, long long g0, int nb, const int *ncnt, const in
     HIPCHK(launch_solve_tq_multi(S.stream, S.kp, dtrees, c, sd, v.tv, g0, nb, ncnt, nidx, infob));
     const int nv = group_var_class(v.nvar);
     HIPCHK(kt_end(S.stream, kt, nv == 2 ? KT_SOLVE_TQ_MULTI2 : nv == 4 ? KT_SOLVE_TQ_MULTI4
-                                                                      : KT_SOLVE_TQ_MULTI8, nb));
+                                                                      : KT_SOLVE_TQ_MULTI8,
+                  (long long)nb * v.lev));
   } else {
     HIPCHK(launch_solve_tq(S.stream, S.kp, false, dtrees, c, sd, g0, nb, ncnt, nidx, nullptr,
                            nullptr, nullptr, nullptr, nullptr, infob));
     HIPCHK(kt_end(S.stream, kt, KT_SOLVE_TQ, nb));
+  }
+  return CWBL_OK;
+}
+
+// ---- CWBL_OPT_COLUMN_SHARE ---------------------------------------------------------------------
+// Why a call of one variable does not run once per column, from what is known before the
+// trees are planned (CWBL_COLUMN_SHARED: it may).  The type rule restates build_family's
+// selection: with no used type of vclr > 0 every tree is 2-D, queried in 2-D and outside the
+// Q1 undefined case; analyze_call checks the planned descriptors themselves afterwards.
+int column_reason(const VarCall &v) {
+  if (!S.column_share) return CWBL_COLUMN_REASON_OFF;
+  if (v.nvar > 1) return CWBL_COLUMN_REASON_GROUP;
+  if (v.sl->nz < 2) return CWBL_COLUMN_REASON_NZ;
+  if (!(record_path() || wave_path() || handoff_path())) return CWBL_COLUMN_REASON_PATH;
+  for (const ObsType &ot : S.obs) {
+    if (ot.nobs <= 0 || (ot.family == 0 && !is_gts_assimilated(ot.type_id))) continue;
+    const cwbl_type_params &tp =
+        ot.family == 0 ? v.vp->gts[ot.type_id - 1] : v.vp->radar[ot.type_id - 1];
+    if (tp.use_it && tp.hclr > 0.0f && tp.vclr > 0.0f) return CWBL_COLUMN_REASON_3D;
+  }
+  return CWBL_COLUMN_SHARED;
+}
+
+// Levels per wavefront of a solve_tq40_column_kernel launch over ncol columns: the option, or
+// all nz unless the columns' waves are fewer than twice what the device holds of this kernel
+// (two waves per SIMD); then the fewest level ranges that reach that many waves.
+int column_levels_per_wave(int ncol, int nz) {
+  int lw = nz;
+  if (S.column_levels > 0) {
+    lw = std::min(S.column_levels, nz);
+  } else {
+    const long long waves = (ncol + 3) / 4, want = 2LL * S.ncu * 4 * 2;
+    if (waves < want) {
+      const long long ranges = std::min<long long>(nz, (want + waves - 1) / waves);
+      lw = (int)((nz + ranges - 1) / ranges);
+    }
+  }
+  return std::max(lw, (nz + 65534) / 65535);  // gridDim.y
+}
+
+// The solves of batch (g0, nb) of a column-shared call: g0 and nb count columns, the lists and
+// infob are the columns'.
+//   record path, option 1   assemble_record_kernel over the columns as it is, then
+//                           solve_tq40_column_kernel over the same records with the whole slab
+//   chunked paths           (option 1 elsewhere, option 2 everywhere) the levels in chunks of up
+//                           to kMaxGroupVars: each chunk is the path's group launch on the column
+//                           view with var[i] = var + (kz0 + i) nx ny and the call's flags for
+//                           every level; a remainder of one level runs the single kernel with
+//                           sd.var offset likewise.  The batch's lists, and on the record path
+//                           its records, serve every chunk.
+int solve_batch_column(VarCall &v, long long g0, int nb, const int *ncnt, const int *nidx,
+                       int2 *infob, hipEvent_t b2, hipEvent_t dn) {
+  const int nz = v.nlev;
+  const long long nxy = (long long)v.full.nx * v.full.ny;
+  float *const var0 = v.full.var;
+  // the view of levels kz0 .. kz0 + n - 1 as a group of n variables (n = 1: a single call)
+  auto chunk = [&](int kz0, int n) {
+    v.sd.var = var0 + nxy * kz0;
+    v.group = n > 1;
+    v.nvar = n;
+    v.lev = n;
+    v.tv.nvar = n;
+    for (int i = 0; i < n; ++i) {
+      v.tv.var[i] = var0 + nxy * (kz0 + i);
+      v.tv.use_rtpp[i] = v.vp->use_rtpp;
+      v.tv.use_rtps[i] = v.vp->use_rtps;
+      v.tv.rtpp_alpha[i] = v.vp->rtpp_alpha;
+      v.tv.rtps_alpha[i] = v.vp->rtps_alpha;
+    }
+  };
+  // the call's own view again, on every return path (finish_call reads tv.var[0])
+  struct Restore {
+    VarCall &v;
+    Tq40Vars tv;
+    SlabDev sd;
+    bool group;
+    ~Restore() {
+      v.tv = tv;
+      v.sd = sd;
+      v.group = group;
+      v.nvar = 1;
+      v.lev = 1;
+    }
+  } restore{v, v.tv, v.sd, v.group};
+  CI.chunk_launches = v.colshare == 1 && record_path() ? 0 : (nz + kMaxGroupVars - 1) / kMaxGroupVars;
+  if (!record_path()) {
+    for (int kz0 = 0; kz0 < nz; kz0 += kMaxGroupVars) {
+      chunk(kz0, std::min(kMaxGroupVars, nz - kz0));
+      if (int rc = solve_batch_path(v, g0, nb, ncnt, nidx, infob, b2, dn)) return rc;
+    }
+    return CWBL_OK;
+  }
+  const TreeDesc *dtrees = S.tdesc.as<TreeDesc>();
+  const long long cap = std::min<long long>(S.tq4_sub > 0 ? S.tq4_sub : nb, 1 << 19);
+  const long long Bs = std::min<long long>(sub_batch(nb, cap), 1 << 19);
+  HIPCHK(S.wsa.ensure((size_t)(Bs + 1) * 8 * AsmRecord<kTq4KP>::WORDS));
+  double *const rec = S.wsa.as<double>();
+  int kt;
+  for (long long s0 = 0; s0 < nb; s0 += Bs) {
+    const int ns = (int)std::min<long long>(Bs, nb - s0);
+    int2 *const inf = infob + s0;
+    HIPCHK(kt_begin(S.stream, &kt));
+    HIPCHK(launch_assemble_record(S.stream, S.kp, dtrees, v.c, restore.sd, g0 + s0, ns,
+                                  ncnt + s0 * v.nt, nidx + s0 * v.list_cap, inf, rec));
+    HIPCHK(kt_end(S.stream, kt, KT_ASSEMBLE_RECORD, ns));
+    if (v.colshare == 1) {
+      const int lw = column_levels_per_wave(ns, nz);
+      CI.levels_per_wave = lw;
+      HIPCHK(kt_begin(S.stream, &kt));
+      HIPCHK(launch_solve_tq40_column(S.stream, S.kp, v.c, v.full, g0 + s0, ns, nz, lw, rec, inf));
+      HIPCHK(kt_end(S.stream, kt, KT_SOLVE_TQ40_COLUMN, (long long)ns * nz));
+      continue;
+    }
+    for (int kz0 = 0; kz0 < nz; kz0 += kMaxGroupVars) {
+      const int n = std::min(kMaxGroupVars, nz - kz0);
+      chunk(kz0, n);
+      HIPCHK(kt_begin(S.stream, &kt));
+      if (n > 1)
+        HIPCHK(launch_solve_tq40_multi(S.stream, S.kp, v.c, v.sd, v.tv, g0 + s0, ns, rec, inf));
+      else
+        HIPCHK(launch_solve_tq40(S.stream, S.kp, v.c, v.sd, g0 + s0, ns, rec, inf));
+      HIPCHK(kt_end(S.stream, kt, n > 1 ? KT_SOLVE_TQ40_MULTI : KT_SOLVE_TQ40, (long long)ns * n));
+    }
   }
   return CWBL_OK;
 }
@@ -1623,12 +1764,12 @@ int finish_call(VarCall &v, cwbl_stats &st) {
     HIPCHK(event(ev, &a));
     HIPCHK(event(ev + 1, &b));
     HIPCHK(hipEventRecord(a, S.stream));
-    SlabDev sdi = v.sd;
+    SlabDev sdi = v.colshare ? v.full : v.sd;  // (a shared call: the slab, not its column view)
     sdi.var = v.tv.var[i];
     int kt;
     HIPCHK(kt_begin(S.stream, &kt));
     HIPCHK(launch_tune_q(S.stream, sdi, S.k));
-    HIPCHK(kt_end(S.stream, kt, KT_TUNE_Q, v.npts));
+    HIPCHK(kt_end(S.stream, kt, KT_TUNE_Q, v.npts * v.nlev));
     HIPCHK(hipEventRecord(b, S.stream));
     v.solve_ev.push_back({ev, ev + 1});
     ev += 2;
@@ -1656,13 +1797,16 @@ int finish_call(VarCall &v, cwbl_stats &st) {
   kt_collect();
   prep_collect();
 
-  st.solved = (long long)ds.solved;
-  st.nobs_sum = (long long)ds.nobs_sum;
+  // (a column-shared call counted its columns: every level of a column has the column's
+  // lists, p and quadrature level, so the per-point call's totals are nlev times these)
+  const long long lev = v.nlev;
+  st.solved = (long long)ds.solved * lev;
+  st.nobs_sum = (long long)ds.nobs_sum * lev;
   // (a hit ran none, or only the uncached batches', of the searches that count this: the
   // inputs being equal, the fill's total holds)
-  st.lz_truncated = v.reuse == 2 ? S.cache.lz_truncated : (long long)ds.lz_truncated;
-  st.nonconverged = (long long)ds.nonconverged;
-  st.sweeps_sum = (long long)ds.sweeps_sum;
+  st.lz_truncated = v.reuse == 2 ? S.cache.lz_truncated : (long long)ds.lz_truncated * lev;
+  st.nonconverged = (long long)ds.nonconverged * lev;
+  st.sweeps_sum = (long long)ds.sweeps_sum * lev;
   st.max_p = (int)ds.max_p;
   st.max_sweeps = (int)ds.max_sweeps;
   st.ms_prep = elapsed(0, 1);
@@ -1756,7 +1900,11 @@ int cwbl_init(const cwbl_init_params *p) {
   S.pageable_register = true;
   S.bin_div = 0;  // 0: by density (bin_div_for)
   S.index_mode = 0;
+  S.column_share = 0;
+  S.column_levels = 0;
+  S.ncu = prop.multiProcessorCount;
   std::memset(&P, 0, sizeof P);
+  std::memset(&CI, 0, sizeof CI);
   S.lead_div = 0;
   S.serial_search = false;
 #ifdef CWBL_DEBUG_KNOBS
@@ -1829,6 +1977,14 @@ int cwbl_set_option(int option, long long value) {
       if (!range(0, 1)) break;
       S.index_mode = (int)value;
       return CWBL_OK;
+    case CWBL_OPT_COLUMN_SHARE:
+      if (!range(0, 2)) break;
+      S.column_share = (int)value;
+      return CWBL_OK;
+    case CWBL_OPT_COLUMN_LEVELS:
+      if (!range(0, 1 << 30)) break;
+      S.column_levels = (int)value;
+      return CWBL_OK;
     case CWBL_OPT_RECORD_REUSE:
       if (!range(0, 1LL << 24)) break;
       S.reuse_budget = (size_t)value << 20;
@@ -1879,6 +2035,13 @@ int cwbl_reuse_info(cwbl_reuse_info_t *out) {
   if (int rc = require_device()) return rc;
   if (!out) return fail(CWBL_ERR_ARG, "cwbl_reuse_info: null argument");
   *out = R;
+  return CWBL_OK;
+}
+
+int cwbl_column_info(cwbl_column_info_t *out) {
+  if (int rc = require_device()) return rc;
+  if (!out) return fail(CWBL_ERR_ARG, "cwbl_column_info: null argument");
+  *out = CI;
   return CWBL_OK;
 }
 
@@ -1978,6 +2141,7 @@ static int begin_call(const cwbl_slab *sl) {
   g_bounce_ms = 0.0;
   std::memset(&P, 0, sizeof P);
   std::memset(&R, 0, sizeof R);
+  std::memset(&CI, 0, sizeof CI);
   g_pspans.clear();
   g_pev_used = 0;
   return CWBL_OK;
@@ -2021,7 +2185,12 @@ static int analyze_call(VarCall &v, cwbl_stats *stats) {
   HIPCHK(hipEventRecord(e0, S.stream));
   // Record reuse: an equal key makes the call a candidate; the coordinates decide.  (A
   // candidate stages its slab first, so its ms_prep holds the staging and the compare.)
-  const bool reuse_on = !v.group && record_path() && S.reuse_budget > 0 && npts > 0;
+  // Column sharing (CWBL_OPT_COLUMN_SHARE): a candidate runs with record reuse off, as a group
+  // call does; the planned trees confirm it below.
+  CI.reason = column_reason(v);
+  const bool col_candidate = CI.reason == CWBL_COLUMN_SHARED;
+  const bool reuse_on =
+      !v.group && !col_candidate && record_path() && S.reuse_budget > 0 && npts > 0;
   RecordKey key;
   bool staged = false;
   if (reuse_on) {
@@ -2047,18 +2216,38 @@ static int analyze_call(VarCall &v, cwbl_stats *stats) {
   }
   st.ntrees = v.nt;
   if (v.nt == 0 || npts == 0) {  // `if(all(.not. succeed)) cycle` (:66)
+    if (col_candidate) CI.reason = CWBL_COLUMN_REASON_NO_TREES;
     HIPCHK(hipStreamSynchronize(S.stream));
     prep_collect();
     return finish();
   }
   for (const TreeDesc &d : v.descs) st.q1_undefined += d.q1_undef ? npts : 0;
   if (v.full_hit) st.q1_undefined = C.q1_undefined;
+  // The planned trees decide whether the call is shared per column, and name the Q1 case.  (A
+  // candidate with a tree that is not 2-D would mean column_reason and build_family disagree:
+  // it runs per point like any other call that is not eligible, with its record reuse off.)
+  for (const TreeDesc &d : v.descs) {
+    if (CI.reason == CWBL_COLUMN_SHARED && (d.tree_dim != 2 || d.query3d))
+      CI.reason = CWBL_COLUMN_REASON_3D;
+    if ((CI.reason == CWBL_COLUMN_SHARED || CI.reason == CWBL_COLUMN_REASON_3D) && d.q1_undef)
+      CI.reason = CWBL_COLUMN_REASON_Q1;
+  }
+  if (CI.reason == CWBL_COLUMN_SHARED) v.colshare = S.column_share;
   HIPCHK(event(1, &e1));
   HIPCHK(hipEventRecord(e1, S.stream));
   HIPCHK(event(2, &e2));
   if (!staged)
     if (int rc = stage_slab(v)) return rc;
   HIPCHK(hipEventRecord(e2, S.stream));
+  if (v.colshare) {  // the batches run over the column view from here on
+    v.full = v.sd;
+    v.sd.nz = 1;
+    v.nlev = sl->nz;
+    v.npts = v.ncol = (long long)sl->ix_lim * sl->iy_lim;
+    CI.shared = 1;
+    CI.columns = v.ncol;
+    CI.levels = v.nlev;
+  }
   plan_batches(v);
   if (v.reuse == 2 && v.plan != C.plan)
     return fail(CWBL_ERR_STATE, "record reuse: the batch plan changed under an equal key");
@@ -2104,7 +2293,11 @@ static int analyze_call(VarCall &v, cwbl_stats *stats) {
     if (v.piped)
       if (int rc = upload_batch_var(v, bi)) return rc;
     HIPCHK(hipEventRecord(b2, S.stream));
-    if (int rc = solve_batch_path(v, g0, nb, ncnt, nidx, infob, b2, dn, crec, hit)) return rc;
+    if (v.colshare) {
+      if (int rc = solve_batch_column(v, g0, nb, ncnt, nidx, infob, b2, dn)) return rc;
+    } else if (int rc = solve_batch_path(v, g0, nb, ncnt, nidx, infob, b2, dn, crec, hit)) {
+      return rc;
+    }
     HIPCHK(hipEventRecord(dn, S.stream));  // this batch's lists are free again
     if (v.piped_back)
       if (int rc = return_batch_var(v, bi, dn)) return rc;

@@ -274,6 +274,15 @@ hipError_t launch_solve_tq40_multi(hipStream_t s, int kp, SolveConsts c, SlabDev
                                    const Tq40Vars &vars, long long g0, int npts, double *ws,
                                    int2 *info);
 
+// CWBL_OPT_COLUMN_SHARE = 1 on the record path: the records are those of the slab's columns
+// (the points kz = 0: a 2-D localisation gives every level of a column the same A and b1), and
+// solve_tq40_column_kernel (cwbl_tq40_column.hip) tridiagonalises once per column and replays
+// the reflectors on the x' of every level.  slab is the whole slab (var, nx, ny, L), g0 and
+// npts count columns; the launch is (ceil(npts / 4), ceil(nz / lw)) with lw levels per wave.
+hipError_t launch_solve_tq40_column(hipStream_t s, int kp, SolveConsts c, SlabDev slab,
+                                    long long g0, int npts, int nz, int lw, double *ws,
+                                    int2 *info);
+
 // The group call of the one-wavefront path (k <= 16, 41..64, and 17..40 without the record
 // split): solve_tq_multi_kernel<KP, NV> (cwbl_tq_multi.hip) is solve_tq_kernel<KP, false> with
 // the x' of up to NV variables carried through one tridiagonalisation.  NV is the class of

@@ -1,7 +1,8 @@
-// cwbl_tq40_common.h — what solve_tq40_kernel (cwbl_tq40.hip) and solve_tq40_multi_kernel
-// (cwbl_tq40_multi.hip) share: the layout (four points per wavefront, one 16-lane DPP row per
-// point; lane l holds the full rows J0 + l + 16 r of A in registers and, for l < J0, row l of
-// the top-left J0 x J0 prefix block), the row sums, the shared-memory struct, dlarfg, the point
+// cwbl_tq40_common.h — what solve_tq40_kernel (cwbl_tq40.hip), solve_tq40_multi_kernel
+// (cwbl_tq40_multi.hip) and solve_tq40_column_kernel (cwbl_tq40_column.hip: the multi kernel's
+// text over the levels of a column) share: the layout (four points per wavefront, one 16-lane
+// DPP row per point; lane l holds the full rows J0 + l + 16 r of A in registers and, for
+// l < J0, row l of the top-left J0 x J0 prefix block), the row sums, the shared-memory struct, dlarfg, the point
 // decode, the record load, the trace and the wave's quadrature rounds.  Every function is
 // inlined into its kernel; the two kernels evaluate the same expressions in the same order, so
 // a variable's analysis is the same bit pattern from either.  The tridiagonalisations (and the
@@ -9,6 +10,18 @@
 // quadrature's level and round loops and the RTPP/RTPS epilogue: each piece here was kept only
 // where both kernels compiled to the registers, LDS and instruction mix they had without it
 // and ran as fast.
+//
+// The twin regions, for whoever changes the numerics (a fix lands in every file that has the
+// region; `single` = cwbl_tq40.hip, `multi` = cwbl_tq40_multi.hip, `column` =
+// cwbl_tq40_column.hip, whose text is multi's except for the loop head, the source of the
+// flags and the info store):
+//   phase 1 and phase 2 of the tridiagonalisation   single (carries x' too, keeps x scal);
+//                                                   multi = column (b1 only, keep x and scal)
+//   quadrature level loop and LDS walk offsets      single = multi = column
+//   replay of the reflectors on x'                  multi = column
+//   quadrature round loop and d                     single = multi = column
+//   back-transform                                  single (from x scal); multi = column
+//   RTPP / RTPS epilogue and the store              single = multi = column
 #pragma once
 
 #include "cwbl_device.h"

@@ -29,12 +29,18 @@ GTS_NVAR = {GTS_SOUND: 4, GTS_SYNOP: 5, GTS_GPSPW: 1, GTS_METAR: 5, GTS_SHIPS: 5
 OPT_SOLVER, OPT_SPLIT40, OPT_SPLIT40_BATCH, OPT_SEARCH = 1, 2, 3, 5
 OPT_BIG_PATH, OPT_BIG_BATCH, OPT_PAGEABLE, OPT_BIN_DIV, OPT_LEAD_DIV, OPT_MAX_BATCH = 6, 7, 8, 9, 10, 11
 OPT_INFO_WINDOW, OPT_INDEX, OPT_RECORD_REUSE = 12, 13, 14
+OPT_COLUMN_SHARE, OPT_COLUMN_LEVELS = 15, 16
 OPTIONS = {"solver": OPT_SOLVER, "split40": OPT_SPLIT40, "split40_batch": OPT_SPLIT40_BATCH,
            "search": OPT_SEARCH,
            "big_path": OPT_BIG_PATH, "big_batch": OPT_BIG_BATCH, "pageable": OPT_PAGEABLE,
            "bin_div": OPT_BIN_DIV, "lead_div": OPT_LEAD_DIV, "max_batch": OPT_MAX_BATCH,
            "info_window": OPT_INFO_WINDOW, "index": OPT_INDEX,
-           "record_reuse": OPT_RECORD_REUSE}
+           "record_reuse": OPT_RECORD_REUSE, "column_share": OPT_COLUMN_SHARE,
+           "column_levels": OPT_COLUMN_LEVELS}
+
+#: cwbl_column_info_t.reason
+(COLUMN_SHARED, COLUMN_REASON_OFF, COLUMN_REASON_3D, COLUMN_REASON_Q1, COLUMN_REASON_NZ,
+ COLUMN_REASON_PATH, COLUMN_REASON_GROUP, COLUMN_REASON_NO_TREES) = range(8)
 
 ERRORS = {1: "CWBL_ERR_ARG", 2: "CWBL_ERR_STATE", 3: "CWBL_ERR_NO_DEVICE", 4: "CWBL_ERR_HIP",
           5: "CWBL_ERR_UNSUPPORTED", 6: "CWBL_ERR_OOM"}
@@ -121,13 +127,22 @@ class ReuseInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class ColumnInfo(C.Structure):
+    _fields_ = [("shared", C.c_int), ("reason", C.c_int), ("columns", C.c_longlong),
+                ("levels", C.c_int), ("levels_per_wave", C.c_int), ("chunk_launches", C.c_int),
+                ("reserved", C.c_int)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
 #: exported symbols of the product library (include/cwb_letkf_core.h)
 EXPORTS = ["cwbl_init", "cwbl_set_stream", "cwbl_set_obs", "cwbl_analyze_var", "cwbl_analyze_vars",
            "cwbl_solve_batch", "cwbl_search",
            "cwbl_pack_columns", "cwbl_unpack_columns", "cwbl_pack_members",
            "cwbl_unpack_members", "cwbl_vcoord_mean", "cwbl_member_sum", "cwbl_scale", "cwbl_set_kernel_timing", "cwbl_kernel_times",
            "cwbl_set_option", "cwbl_bin_index", "cwbl_prep_info", "cwbl_reuse_info",
-           "cwbl_finalize", "cwbl_last_error", "cwbl_abi_version"]
+           "cwbl_column_info", "cwbl_finalize", "cwbl_last_error", "cwbl_abi_version"]
 
 
 def _ptr(a):
@@ -312,6 +327,7 @@ def load_library(path=None):
                                    C.c_longlong, vp, vp, C.c_int]
     lib.cwbl_prep_info.argtypes = [C.POINTER(PrepInfo)]
     lib.cwbl_reuse_info.argtypes = [C.POINTER(ReuseInfo)]
+    lib.cwbl_column_info.argtypes = [C.POINTER(ColumnInfo)]
     lib.cwbl_finalize.argtypes = []
     lib.cwbl_last_error.restype = cp
     lib.cwbl_abi_version.restype = C.c_int
@@ -321,7 +337,7 @@ def load_library(path=None):
                "cwbl_unpack_members", "cwbl_vcoord_mean",
                "cwbl_member_sum", "cwbl_scale", "cwbl_set_kernel_timing", "cwbl_kernel_times",
                "cwbl_set_option", "cwbl_bin_index", "cwbl_prep_info", "cwbl_reuse_info",
-               "cwbl_finalize"):
+               "cwbl_column_info", "cwbl_finalize"):
         getattr(lib, fn).restype = C.c_int
     return lib
 
@@ -452,6 +468,13 @@ class Core:
         """cwbl_reuse_info: what the last analyze_var solved from kept records (ReuseInfo)."""
         info = ReuseInfo()
         self._check(self.lib.cwbl_reuse_info(C.byref(info)))
+        return info
+
+    def column_info(self):
+        """cwbl_column_info: whether the last analyze_var ran once per column under the
+        "column_share" option, and if not why (ColumnInfo; reason: COLUMN_REASON_*)."""
+        info = ColumnInfo()
+        self._check(self.lib.cwbl_column_info(C.byref(info)))
         return info
 
     # ---- member <-> column transposes (device pointers; see cwbl/transpose.py) ----------

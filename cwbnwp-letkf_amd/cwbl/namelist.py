@@ -383,6 +383,34 @@ def var_names(cfg):
     return out
 
 
+# ---- variables that localise in 2-D only (CWBL_OPT_COLUMN_SHARE) -----------------------------
+def _used_types(vp):
+    """The type blocks of vp that the configuration lets build a tree: use_it, hclr > 0 and,
+    for a GTS type, at least one assimilated obs variable."""
+    for t in vp.gts:
+        if t.use_it and t.hclr > 0.0 and any(t.is_assim):
+            yield t
+    for t in vp.radar:
+        if t.use_it and t.hclr > 0.0:
+            yield t
+
+
+def column_shared_vars(cfg):
+    """The names of the var_update entries that cwbl_analyze_var can analyse once per column
+    under options={"column_share": 1}: those with at least one used obs type (use_it,
+    hclr > 0 and, for a GTS type, any is_assim) whose used types all have vclr <= 0, so that
+    no type localises vertically and the weights of a grid point depend on its column alone.
+    This is the host-side mirror, for planning from the configuration; the library's own check
+    decides (it also looks at which types have obs, at nz, the solver and the path, and
+    Core.column_info() reports what a call did)."""
+    out = []
+    for i, name in enumerate(var_names(cfg)):
+        used = list(_used_types(var_params(cfg, i + 1)))
+        if used and all(t.vclr <= 0.0 for t in used):
+            out.append(name)
+    return out
+
+
 # ---- groups of variables for cwbl_analyze_vars ----------------------------------------------
 _GRID_TAGS = {"U": "u", "V": "v", "W": "w", "PH": "w", "MU": "2d"}
 

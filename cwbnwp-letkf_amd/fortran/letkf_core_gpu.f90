@@ -72,6 +72,11 @@ module letkf_core_gpu
     integer(c_int), parameter, public :: CWBL_OPT_INDEX = 13
     ! cwbl_set_option: MiB of assembled records kept for the next variable (0 = no reuse)
     integer(c_int), parameter, public :: CWBL_OPT_RECORD_REUSE = 14
+    ! cwbl_set_option: a variable whose obs types all localise in 2-D analysed once per column
+    ! (0 off, 1 the column kernel / level-chunked group kernels, 2 the chunked kernels only)
+    integer(c_int), parameter, public :: CWBL_OPT_COLUMN_SHARE = 15
+    ! cwbl_set_option: levels per wavefront of the column kernel (0 = automatic)
+    integer(c_int), parameter, public :: CWBL_OPT_COLUMN_LEVELS = 16
 
     type, bind(C), public :: cwbl_bin_grid         ! cwbl_bin_index
         real(c_float)  :: x0, y0, z0, binv
@@ -88,6 +93,12 @@ module letkf_core_gpu
         real(c_double)       :: ms_compare
     end type cwbl_reuse_info_t
 
+    type, bind(C), public :: cwbl_column_info_t    ! cwbl_column_info
+        integer(c_int)       :: shared, reason
+        integer(c_long_long) :: columns
+        integer(c_int)       :: levels, levels_per_wave, chunk_launches, reserved
+    end type cwbl_column_info_t
+
     ! projection_nml (module_config.f90:70-75), include/cwb_letkf_ingest.h
     type, bind(C), public :: cwbl_projection
         real(c_float) :: sta_lon, cen_lat, truelat1, truelat2
@@ -101,7 +112,7 @@ module letkf_core_gpu
               cwbl_pack_columns, cwbl_unpack_columns, cwbl_pack_members, cwbl_unpack_members, &
               cwbl_vcoord_mean, &
               cwbl_member_sum, cwbl_scale, cwbl_set_stream, cwbl_set_option, &
-              cwbl_bin_index, cwbl_prep_info, cwbl_reuse_info, &
+              cwbl_bin_index, cwbl_prep_info, cwbl_reuse_info, cwbl_column_info, &
               cwbl_finalize, cwbl_abi_version, cwbl_error, cwbl_check
     ! host obs ingest (include/cwb_letkf_ingest.h); file names and varname are passed as
     ! trim(name)//c_null_char
@@ -317,6 +328,12 @@ module letkf_core_gpu
             import :: c_int, cwbl_reuse_info_t
             type(cwbl_reuse_info_t), intent(out) :: info
         end function cwbl_reuse_info
+
+        ! whether the last cwbl_analyze_var ran once per column (CWBL_OPT_COLUMN_SHARE)
+        integer(c_int) function cwbl_column_info(info) bind(C, name='cwbl_column_info')
+            import :: c_int, cwbl_column_info_t
+            type(cwbl_column_info_t), intent(out) :: info
+        end function cwbl_column_info
 
         integer(c_int) function cwbl_finalize() bind(C, name='cwbl_finalize')
             import :: c_int

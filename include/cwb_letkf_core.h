@@ -353,7 +353,7 @@ enum {
                                 * by a host thread and used only where a list truncates (or
                                 * for every point with CWBL_OPT_SEARCH = 1).  Cached indexes
                                 * of the two modes are kept apart */
-  CWBL_OPT_RECORD_REUSE = 14   /* k = 17..40 record path: device memory budget in MiB for the
+  CWBL_OPT_RECORD_REUSE = 14,  /* k = 17..40 record path: device memory budget in MiB for the
                                 * assembled records kept from one cwbl_analyze_var to the next
                                 * (0 = no reuse; default min(40 GiB, 40% of the device memory
                                 * free at cwbl_init)).  A call whose obs set, options, type
@@ -362,6 +362,28 @@ enum {
                                 * QC columns, the search and the assembly: bit-identical
                                 * results.  A budget below the slab's need keeps the leading
                                 * batches that fit */
+  CWBL_OPT_COLUMN_SHARE = 15,  /* cwbl_analyze_var of a variable whose used obs types all have
+                                * vclr <= 0 (2-D localisation: the weights of a grid point then
+                                * depend on its column only): 0 every point on its own (default);
+                                * 1 one search, one assembly and one tridiagonalisation per
+                                * column, every level solved from that factor: on the k = 17..40
+                                * record path solve_tq40_column_kernel, on the one-wavefront and
+                                * hand-off paths the group kernels over chunks of up to
+                                * CWBL_MAX_GROUP_VARS levels; 2 the level-chunked group kernels on
+                                * the record path too (the A/B partner of 1).  Equal counters.
+                                * Results bit-identical to option 0 on the one-wavefront and
+                                * hand-off paths; on the record path when ix_lim * iy_lim is a
+                                * multiple of 4 or no wavefront of four points mixes quadrature
+                                * round classes (see cwbl_column_info), otherwise equal within
+                                * the parity bar.  A call that is not eligible (see
+                                * cwbl_column_info) runs as under 0; a shared call runs with
+                                * record reuse off (the cache is not read, filled or
+                                * invalidated).  cwbl_analyze_vars with two or more variables
+                                * ignores the option */
+  CWBL_OPT_COLUMN_LEVELS = 16  /* levels per wavefront of solve_tq40_column_kernel, >= 1 (0 =
+                                * automatic, default: all levels of the column unless the
+                                * columns alone do not fill the device).  The result does not
+                                * depend on it; tests use it to force level splits */
 };
 int         cwbl_set_option(int option, long long value);
 
@@ -411,6 +433,49 @@ typedef struct cwbl_reuse_info_t {
                                  * synchronisation included (0: the key already differed) */
 } cwbl_reuse_info_t;
 int         cwbl_reuse_info(cwbl_reuse_info_t *out);
+
+/* What the last cwbl_analyze_var (or cwbl_analyze_vars) did under CWBL_OPT_COLUMN_SHARE.
+ *
+ * Bit identity with option 0.  The one-wavefront and hand-off kernels solve one point per
+ * wavefront, and a shared call's result there equals option 0's bit for bit.  The record
+ * path's kernels solve four points per wavefront, and the wavefront runs the quadrature rule
+ * of the largest round class (15, 23, 31 or 63 nodes: spectrum bound M/m up to 1e3, 1e5, 1e12,
+ * beyond) among its four points.  Option 0 puts the points g = 4n .. 4n + 3 of the slab
+ * (g = i + ix_lim (j + iy_lim kz)) in a wavefront, a shared call the columns 4n .. 4n + 3 at
+ * every level.  The two groupings are the same when ix_lim * iy_lim is a multiple of 4; then,
+ * or whenever no wavefront of either grouping mixes round classes, the results are equal bit
+ * for bit.  Otherwise a point of a lower class may run a longer rule under one option than
+ * under the other: both results meet the parity bar (the rules agree to ~1e-12 relative, far
+ * below the fp32 rounding of the analysis), the low bits of some values differ.  Options 1 and
+ * 2 always agree with each other bit for bit, whatever CWBL_OPT_COLUMN_LEVELS.
+ *
+ * Eligibility.  A call is shared when the option is non-zero, it analyses one variable, nz >= 2, the default
+ * solver runs on the record, the one-wavefront or the hand-off path, and every tree of the
+ * call is 2-D with a 2-D query and outside the Q1 undefined case; the check is made after the
+ * trees are planned, before any batch work. */
+enum {
+  CWBL_COLUMN_SHARED = 0,         /* shared (reason of a shared call) */
+  CWBL_COLUMN_REASON_OFF = 1,     /* the option is 0 */
+  CWBL_COLUMN_REASON_3D = 2,      /* a used obs type has vclr > 0 */
+  CWBL_COLUMN_REASON_Q1 = 3,      /* a family in the Q1 undefined case (CWBL_Q1_REPLICATE) */
+  CWBL_COLUMN_REASON_NZ = 4,      /* nz < 2 */
+  CWBL_COLUMN_REASON_PATH = 5,    /* CWBL_OPT_SOLVER = 1, or k > 64 under CWBL_OPT_BIG_PATH = 0 */
+  CWBL_COLUMN_REASON_GROUP = 6,   /* cwbl_analyze_vars with two or more variables */
+  CWBL_COLUMN_REASON_NO_TREES = 7 /* nothing to assimilate: no tree, no analysis */
+};
+typedef struct cwbl_column_info_t {
+  int       shared;           /* 1: the call ran once per column */
+  int       reason;           /* CWBL_COLUMN_REASON_* when not shared, else CWBL_COLUMN_SHARED */
+  long long columns;          /* ix_lim * iy_lim (0 when not shared) */
+  int       levels;           /* nz (0 when not shared) */
+  int       levels_per_wave;  /* solve_tq40_column_kernel: levels per wavefront of the last
+                               * launch; 0 on the chunked paths */
+  int       chunk_launches;   /* chunked paths: launches per (sub-)batch, one per chunk of up
+                               * to CWBL_MAX_GROUP_VARS levels (a remainder of one level runs
+                               * the single kernel and counts); 0 for the column kernel */
+  int       reserved;
+} cwbl_column_info_t;
+int         cwbl_column_info(cwbl_column_info_t *out);
 
 int         cwbl_finalize(void);
 const char *cwbl_last_error(void);
