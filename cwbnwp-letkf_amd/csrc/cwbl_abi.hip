@@ -223,7 +223,7 @@ struct TreeBufs {
 
 enum KernelId {
   KT_SEARCH_BINNED, KT_SEARCH_FLAGGED, KT_SEARCH_TREE, KT_ASSEMBLE_RECORD, KT_SOLVE_TQ40,
-  KT_SOLVE_TQ40_MULTI, KT_SOLVE_TQ40_COLUMN, KT_SOLVE_TQ_MULTI2, KT_SOLVE_TQ_MULTI4, KT_SOLVE_TQ_MULTI8,
+  KT_SOLVE_TQ40_MULTI, KT_SOLVE_TQ40_COLUMN, KT_FILL_TQ40_FACTOR, KT_SOLVE_TQ40_FACTOR, KT_SOLVE_TQ_MULTI2, KT_SOLVE_TQ_MULTI4, KT_SOLVE_TQ_MULTI8,
   KT_BIG_HANDOFF, KT_TQB_TAIL, KT_BIG_HANDOFF_MULTI2, KT_BIG_HANDOFF_MULTI4,
   KT_BIG_HANDOFF_MULTI8, KT_TQB_TAIL_MULTI2, KT_TQB_TAIL_MULTI4, KT_TQB_TAIL_MULTI8,
   KT_SOLVE_TQ, KT_SOLVE_TQ_BIG, KT_SOLVE_JACOBI, KT_TUNE_Q,
@@ -237,6 +237,10 @@ struct KTime { long long launches = 0, points = 0; double ms = 0.0; };
 // function, multi_infl and the point coordinates, not of the analysed variable (var enters in
 // solve_tq40_kernel only).  A later call with an equal key and bit-equal coordinates launches
 // the solves on the kept records and nothing before them.
+// Factor reuse (CWBL_OPT_FACTOR_REUSE, the default): the fill's solve, fill_tq40_factor_kernel,
+// leaves each cached point's factor A = Q T Q^T in its record's words (FactorRecord), and a hit
+// runs solve_tq40_factor_kernel on those, without the tridiagonalisation.  A cache holds one
+// form only: the option bumps the generation, which is part of the key.
 struct RecordKey {
   unsigned long long gen;  // State::gen: obs set, cwbl_init constants, options
   float multi_infl;        // inflat is on the record's diagonal
@@ -331,6 +335,7 @@ struct State {
   size_t handoff_budget = 0;                          // bytes for the k > 64 hand-off records
   unsigned long long gen = 0;     // bumped by cwbl_init, cwbl_set_obs and cwbl_set_option
   size_t reuse_budget = 0;        // CWBL_OPT_RECORD_REUSE in bytes (0: no reuse)
+  bool factor_reuse = true;       // CWBL_OPT_FACTOR_REUSE: the cache keeps factors, not records
   int column_share = 0;           // CWBL_OPT_COLUMN_SHARE: 0 off, 1 column kernel, 2 chunks only
   int column_levels = 0;          // CWBL_OPT_COLUMN_LEVELS: levels per wave (0: automatic)
   int ncu = 0;                    // compute units of the device (automatic level split)
@@ -485,6 +490,8 @@ std::string kernel_name(int id) {
     case KT_SOLVE_TQ40: return "solve_tq40_kernel<" + kp + ", 0>";
     case KT_SOLVE_TQ40_MULTI: return "solve_tq40_multi_kernel<" + kp + ">";
     case KT_SOLVE_TQ40_COLUMN: return "solve_tq40_column_kernel<" + kp + ">";
+    case KT_FILL_TQ40_FACTOR: return "fill_tq40_factor_kernel<" + kp + ">";
+    case KT_SOLVE_TQ40_FACTOR: return "solve_tq40_factor_kernel<" + kp + ">";
     case KT_BIG_HANDOFF:
       return S.kp == 128 ? "solve_tq_rows_kernel<128, 64>"
                          : "solve_tq_big_kernel<" + kp + ", false, " +
@@ -1532,8 +1539,16 @@ int solve_batch_path(VarCall &v, long long g0, int nb, const int *ncnt, const in
     // a cached batch keeps every sub-batch's records, S.wsa only the current one's
     const size_t rstep = crec ? AsmRecord<kTq4KP>::WORDS : 0;
     // the solve of n points from g: one variable's, or the group's over all its variables
-    const int kt_solve = v.group ? KT_SOLVE_TQ40_MULTI : KT_SOLVE_TQ40;
+    // A cached batch under CWBL_OPT_FACTOR_REUSE keeps factors: its fill solves with
+    // fill_tq40_factor_kernel, which leaves the factor over each record, and a hit with
+    // solve_tq40_factor_kernel.  (A group call never has a cached batch.)
+    const bool factor = crec && S.factor_reuse && !v.group;
+    const int kt_solve = factor ? (hit ? KT_SOLVE_TQ40_FACTOR : KT_FILL_TQ40_FACTOR)
+                         : v.group ? KT_SOLVE_TQ40_MULTI : KT_SOLVE_TQ40;
     auto solve = [&](long long g, int n, double *r, int2 *inf) {
+      if (factor)
+        return hit ? launch_solve_tq40_factor(S.stream, S.kp, c, sd, g, n, r, inf)
+                   : launch_fill_tq40_factor(S.stream, S.kp, c, sd, g, n, r, inf);
       return v.group ? launch_solve_tq40_multi(S.stream, S.kp, c, sd, v.tv, g, n, r, inf)
                      : launch_solve_tq40(S.stream, S.kp, c, sd, g, n, r, inf);
     };
@@ -1902,6 +1917,7 @@ int cwbl_init(const cwbl_init_params *p) {
   S.index_mode = 0;
   S.column_share = 0;
   S.column_levels = 0;
+  S.factor_reuse = true;
   S.ncu = prop.multiProcessorCount;
   std::memset(&P, 0, sizeof P);
   std::memset(&CI, 0, sizeof CI);
@@ -1989,6 +2005,10 @@ int cwbl_set_option(int option, long long value) {
       if (!range(0, 1LL << 24)) break;
       S.reuse_budget = (size_t)value << 20;
       S.cache.release();  // the next fill allocates within the new budget
+      return CWBL_OK;
+    case CWBL_OPT_FACTOR_REUSE:
+      if (!range(0, 1)) break;
+      S.factor_reuse = value == 1;  // (the new generation voids a cache of the other form)
       return CWBL_OK;
     default:
       return fail(CWBL_ERR_ARG, "cwbl_set_option: unknown option %d", option);

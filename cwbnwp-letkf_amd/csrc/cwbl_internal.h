@@ -253,11 +253,37 @@ struct AsmRecord {
   static constexpr int U1 = KP * (KP + 1) / 2;   // b1 = Yb d (KP)
   static constexpr int WORDS = (U1 + KP + 1) / 2 * 2;
 };
+// What the record cache keeps of a point under CWBL_OPT_FACTOR_REUSE, in the record's own
+// words: the factor A = Q T Q^T as LAPACK's dsytrd stores it, with alpha_j = A(j + 1, j) as
+// step j's dlarfg read it where dsytrd would put e_j (beta, tau and scal are recomputed from
+// alpha and x, bit for bit), and Q^T b1.  Column j = 0 .. KP-3 is stored by row, rows
+// j + 1 .. KP-1 (alpha_j, then the unscaled, masked pivot column x), so that the 16 lanes of a
+// DPP row read 16 consecutive words.
+template <int KP>
+struct FactorRecord {
+  static constexpr int D = 0;         // diagonal of T (KP)
+  static constexpr int U1 = KP;       // Q^T b1 (KP)
+  static constexpr int COL = 2 * KP;  // the columns
+  // row j + 1 of column j; row i >= j + 1 at col(j) + i - (j + 1)
+  static constexpr int col(int j) { return COL + j * (KP - 1) - j * (j - 1) / 2; }
+  static constexpr int EL = col(KP - 2);  // c(KP-2, KP-1): the trailing 2 x 2's off-diagonal
+  static constexpr int WORDS = EL + 1;
+};
+static_assert(FactorRecord<kTq4KP>::WORDS == AsmRecord<kTq4KP>::WORDS,
+              "a factor takes its record's slot");
 hipError_t launch_assemble_record(hipStream_t s, int kp, const TreeDesc *trees, SolveConsts c,
                                   SlabDev slab, long long g0, int npts, const int *nbr_cnt,
                                   const int *nbr_idx, int2 *info, double *ws);
 hipError_t launch_solve_tq40(hipStream_t s, int kp, SolveConsts c, SlabDev slab, long long g0,
                              int npts, double *ws, int2 *info);
+// The record cache's pair (cwbl_tq40_fill.hip): fill_tq40_factor_kernel is solve_tq40_kernel's
+// analysis from the records `ws`, which it leaves as FactorRecords; solve_tq40_factor_kernel is
+// the same analysis from those.  Same launch contract as launch_solve_tq40 (the spare record
+// included).
+hipError_t launch_fill_tq40_factor(hipStream_t s, int kp, SolveConsts c, SlabDev slab,
+                                   long long g0, int npts, double *ws, int2 *info);
+hipError_t launch_solve_tq40_factor(hipStream_t s, int kp, SolveConsts c, SlabDev slab,
+                                    long long g0, int npts, const double *ws, int2 *info);
 
 // cwbl_analyze_vars: the variables of a group share the record (A, b1) and so the factor
 // A = Q T Q^T; solve_tq40_multi_kernel (cwbl_tq40_multi.hip) tridiagonalises once per point

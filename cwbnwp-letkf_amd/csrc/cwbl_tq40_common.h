@@ -14,14 +14,20 @@
 // The twin regions, for whoever changes the numerics (a fix lands in every file that has the
 // region; `single` = cwbl_tq40.hip, `multi` = cwbl_tq40_multi.hip, `column` =
 // cwbl_tq40_column.hip, whose text is multi's except for the loop head, the source of the
-// flags and the info store):
+// flags and the info store; `fill` and `factor` = fill_tq40_factor_kernel and
+// solve_tq40_factor_kernel in cwbl_tq40_fill.hip, which share one text, tq40_factor_solve, for
+// everything after the factor: multi's loop body at one variable, with Q^T b1, the accepted
+// count and the var index re-read or recomputed at their uses):
 //   phase 1 and phase 2 of the tridiagonalisation   single (carries x' too, keeps x scal);
-//                                                   multi = column (b1 only, keep x and scal)
-//   quadrature level loop and LDS walk offsets      single = multi = column
-//   replay of the reflectors on x'                  multi = column
-//   quadrature round loop and d                     single = multi = column
-//   back-transform                                  single (from x scal); multi = column
-//   RTPP / RTPS epilogue and the store              single = multi = column
+//                                                   multi = column = fill (b1 only, keep x and
+//                                                   scal; fill also keeps each step's alpha)
+//   per-step dlarfg from the stored alpha and x     factor (xx: the steps' own chains)
+//   quadrature level loop and LDS walk offsets      single = multi = column = fill/factor
+//   replay of the reflectors on x'                  multi = column = fill/factor
+//   quadrature round loop and d                     single = multi = column = fill/factor
+//   back-transform                                  single (from x scal);
+//                                                   multi = column = fill/factor
+//   RTPP / RTPS epilogue and the store              single = multi = column = fill/factor
 #pragma once
 
 #include "cwbl_device.h"

@@ -77,6 +77,9 @@ module letkf_core_gpu
     integer(c_int), parameter, public :: CWBL_OPT_COLUMN_SHARE = 15
     ! cwbl_set_option: levels per wavefront of the column kernel (0 = automatic)
     integer(c_int), parameter, public :: CWBL_OPT_COLUMN_LEVELS = 16
+    ! cwbl_set_option: the record cache keeps each point's factor A = Q T Q^T (1, default) or
+    ! its assembled record (0)
+    integer(c_int), parameter, public :: CWBL_OPT_FACTOR_REUSE = 17
 
     type, bind(C), public :: cwbl_bin_grid         ! cwbl_bin_index
         real(c_float)  :: x0, y0, z0, binv

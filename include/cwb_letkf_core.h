@@ -380,10 +380,17 @@ enum {
                                 * record reuse off (the cache is not read, filled or
                                 * invalidated).  cwbl_analyze_vars with two or more variables
                                 * ignores the option */
-  CWBL_OPT_COLUMN_LEVELS = 16  /* levels per wavefront of solve_tq40_column_kernel, >= 1 (0 =
+  CWBL_OPT_COLUMN_LEVELS = 16, /* levels per wavefront of solve_tq40_column_kernel, >= 1 (0 =
                                 * automatic, default: all levels of the column unless the
                                 * columns alone do not fill the device).  The result does not
                                 * depend on it; tests use it to force level splits */
+  CWBL_OPT_FACTOR_REUSE = 17   /* what CWBL_OPT_RECORD_REUSE keeps of a point, in the same
+                                * 6880 bytes: 1 (default) the factor A = Q T Q^T of the record,
+                                * written over it by the call that fills the cache, so a later
+                                * call with an equal key skips the tridiagonalisation as well;
+                                * 0 the assembled record itself, tridiagonalised again by every
+                                * call.  Bit-identical results either way; budget, key,
+                                * counters and cwbl_reuse_info do not depend on it */
 };
 int         cwbl_set_option(int option, long long value);
 
