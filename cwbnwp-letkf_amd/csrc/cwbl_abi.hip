@@ -239,7 +239,9 @@ struct KTime { long long launches = 0, points = 0; double ms = 0.0; };
 // the solves on the kept records and nothing before them.
 // Factor reuse (CWBL_OPT_FACTOR_REUSE, the default): the fill's solve, fill_tq40_factor_kernel,
 // leaves each cached point's factor A = Q T Q^T in its record's words (FactorRecord), and a hit
-// runs solve_tq40_factor_kernel on those, without the tridiagonalisation.  A cache holds one
+// runs solve_tq40_factor_kernel on those, without the tridiagonalisation.  The steps' beta and
+// tau go to an entry of their own per cached record (FactorAux), outside the budget, which
+// bounds the records alone: what is cached does not depend on the form.  A cache holds one
 // form only: the option bumps the generation, which is part of the key.
 struct RecordKey {
   unsigned long long gen;  // State::gen: obs set, cwbl_init constants, options
@@ -255,7 +257,9 @@ struct RecordCache {
   // off[b] of `rec`; sub-batch s0 of it starts s0 records on, its spare being the next
   // sub-batch's first record.  info: (p, level) of the pts cached points as the fill left
   // them; a hit restores p.  sx, sy, salt: the coordinates the records were assembled from.
-  DevBuf rec, info, sx, sy, salt, flag;
+  // aux (factor reuse only): one FactorAux per record of `rec`, spares included, by the same
+  // ordinal: batch b's entries start at entry off[b] / WORDS, sub-batch s0's s0 entries on.
+  DevBuf rec, aux, info, sx, sy, salt, flag;
   PinBuf hflag;
   std::vector<std::pair<long long, int>> plan;
   std::vector<size_t> off;
@@ -264,10 +268,10 @@ struct RecordCache {
   // what a call that skips plan_trees and the searches still reports
   int nt = 0, list_cap = 0;
   long long lz_truncated = 0, q1_undefined = 0;
-  size_t bytes() const { return rec.n + info.n + sx.n + sy.n + salt.n + flag.n; }
+  size_t bytes() const { return rec.n + aux.n + info.n + sx.n + sy.n + salt.n + flag.n; }
   void release() {
     valid = false;
-    for (DevBuf *b : {&rec, &info, &sx, &sy, &salt, &flag}) b->release();
+    for (DevBuf *b : {&rec, &aux, &info, &sx, &sy, &salt, &flag}) b->release();
     hflag.release();
     plan.clear();
     off.clear();
@@ -1130,6 +1134,15 @@ int begin_fill(VarCall &v, const RecordKey &key) {
   const size_t need = words * sizeof(double);
   bool ok = need <= C.rec.n ||
             C.rec.ensure(std::min(S.reuse_budget, need + need / 16)) == hipSuccess;
+  // The steps' scalars of the factors, an entry per record: beside the budget's cut, like info
+  // and the snapshot, with the same headroom; a cache of records holds none
+  if (S.factor_reuse) {
+    const size_t aneed =
+        words / AsmRecord<kTq4KP>::WORDS * FactorAux<kTq4KP>::WORDS * sizeof(double);
+    ok = ok && (aneed <= C.aux.n || C.aux.ensure(aneed + aneed / 16) == hipSuccess);
+  } else {
+    C.aux.release();
+  }
   ok = ok && C.info.ensure((size_t)C.pts * sizeof(int2)) == hipSuccess;
   ok = ok && C.sx.ensure(C.nxy * 4) == hipSuccess && C.sy.ensure(C.nxy * 4) == hipSuccess;
   ok = ok && C.salt.ensure(C.nalt * 4) == hipSuccess && C.flag.ensure(sizeof(int)) == hipSuccess;
@@ -1519,10 +1532,11 @@ long long sub_batch(int nb, long long cap) {
 //                group call; CWBL_OPT_SOLVER = 1: the Jacobi eigensolver kernel (k <= 64)
 // b2 / dn: the events around the batch's solve (the record path times its kernel pair
 // between them).  crec (record path): the batch's region of the record cache, which a fill
-// assembles into and a hit (no lists, no assembly) solves from; null: S.wsa.
+// assembles into and a hit (no lists, no assembly) solves from; null: S.wsa.  caux: that
+// region's FactorAux entries (a cached batch under factor reuse; else null and unused).
 int solve_batch_path(VarCall &v, long long g0, int nb, const int *ncnt, const int *nidx,
                      int2 *infob, hipEvent_t b2, hipEvent_t dn, double *crec = nullptr,
-                     bool hit = false) {
+                     bool hit = false, double *caux = nullptr) {
   const TreeDesc *dtrees = S.tdesc.as<TreeDesc>();
   const SolveConsts &c = v.c;
   const SlabDev &sd = v.sd;
@@ -1546,9 +1560,12 @@ int solve_batch_path(VarCall &v, long long g0, int nb, const int *ncnt, const in
     const int kt_solve = factor ? (hit ? KT_SOLVE_TQ40_FACTOR : KT_FILL_TQ40_FACTOR)
                          : v.group ? KT_SOLVE_TQ40_MULTI : KT_SOLVE_TQ40;
     auto solve = [&](long long g, int n, double *r, int2 *inf) {
-      if (factor)
-        return hit ? launch_solve_tq40_factor(S.stream, S.kp, c, sd, g, n, r, inf)
-                   : launch_fill_tq40_factor(S.stream, S.kp, c, sd, g, n, r, inf);
+      if (factor) {
+        // (the entries of the records r: the same ordinal within the batch's region)
+        double *const ax = caux + (size_t)(r - rec) / rstep * FactorAux<kTq4KP>::WORDS;
+        return hit ? launch_solve_tq40_factor(S.stream, S.kp, c, sd, g, n, r, ax, inf)
+                   : launch_fill_tq40_factor(S.stream, S.kp, c, sd, g, n, r, ax, inf);
+      }
       return v.group ? launch_solve_tq40_multi(S.stream, S.kp, c, sd, v.tv, g, n, r, inf)
                      : launch_solve_tq40(S.stream, S.kp, c, sd, g, n, r, inf);
     };
@@ -2305,6 +2322,9 @@ static int analyze_call(VarCall &v, cwbl_stats *stats) {
     HIPCHK(event(ev + 3, &dn));
     // a cached batch: its region of the record cache; on a hit neither lists nor assembly
     double *const crec = bi < v.ncached ? C.rec.as<double>() + C.off[bi] : nullptr;
+    const size_t aoff =
+        crec ? C.off[bi] / AsmRecord<kTq4KP>::WORDS * FactorAux<kTq4KP>::WORDS : 0;
+    double *const caux = crec && S.factor_reuse ? C.aux.as<double>() + aoff : nullptr;
     const bool hit = crec && v.reuse == 2;
     if (!hit) {
       if (int rc = search_batch(v, bi, ncnt, nidx, a, b)) return rc;
@@ -2315,7 +2335,8 @@ static int analyze_call(VarCall &v, cwbl_stats *stats) {
     HIPCHK(hipEventRecord(b2, S.stream));
     if (v.colshare) {
       if (int rc = solve_batch_column(v, g0, nb, ncnt, nidx, infob, b2, dn)) return rc;
-    } else if (int rc = solve_batch_path(v, g0, nb, ncnt, nidx, infob, b2, dn, crec, hit)) {
+    } else if (int rc = solve_batch_path(v, g0, nb, ncnt, nidx, infob, b2, dn, crec, hit,
+                                       caux)) {
       return rc;
     }
     HIPCHK(hipEventRecord(dn, S.stream));  // this batch's lists are free again

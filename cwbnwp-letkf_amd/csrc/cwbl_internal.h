@@ -254,11 +254,12 @@ struct AsmRecord {
   static constexpr int WORDS = (U1 + KP + 1) / 2 * 2;
 };
 // What the record cache keeps of a point under CWBL_OPT_FACTOR_REUSE, in the record's own
-// words: the factor A = Q T Q^T as LAPACK's dsytrd stores it, with alpha_j = A(j + 1, j) as
-// step j's dlarfg read it where dsytrd would put e_j (beta, tau and scal are recomputed from
-// alpha and x, bit for bit), and Q^T b1.  Column j = 0 .. KP-3 is stored by row, rows
-// j + 1 .. KP-1 (alpha_j, then the unscaled, masked pivot column x), so that the 16 lanes of a
-// DPP row read 16 consecutive words.
+// words: the factor A = Q T Q^T as LAPACK's dsytrd stores it, with step j's scal (the factor
+// dlarfg scales x by) where dsytrd would put e_j, and Q^T b1.  Column j = 0 .. KP-3 is stored by
+// row, rows j + 1 .. KP-1 (scal_j, then the unscaled, masked pivot column x), so that the 16
+// lanes of a DPP row read 16 consecutive words; scal_j lies where solve_tq40_multi_kernel's
+// layout keeps it (word 0 of sm.pv's column in phase 1, row j + 1 of the column's registers in
+// phase 2).  T's off-diagonal and the steps' tau are the point's FactorAux.
 template <int KP>
 struct FactorRecord {
   static constexpr int D = 0;         // diagonal of T (KP)
@@ -266,11 +267,24 @@ struct FactorRecord {
   static constexpr int COL = 2 * KP;  // the columns
   // row j + 1 of column j; row i >= j + 1 at col(j) + i - (j + 1)
   static constexpr int col(int j) { return COL + j * (KP - 1) - j * (j - 1) / 2; }
-  static constexpr int EL = col(KP - 2);  // c(KP-2, KP-1): the trailing 2 x 2's off-diagonal
+  static constexpr int EL = col(KP - 2);  // unused (FactorAux::B holds c(KP-2, KP-1)): keeps WORDS
   static constexpr int WORDS = EL + 1;
 };
 static_assert(FactorRecord<kTq4KP>::WORDS == AsmRecord<kTq4KP>::WORDS,
               "a factor takes its record's slot");
+// The steps' scalars of a cached factor, an entry per record in a buffer of its own (same
+// ordinal as the record): the bits the fill's dlarfg produced, so that a hit runs none.
+//   B + i: T's off-diagonal as sm.tq[q][i][1] holds it: 0 at i = 0, beta_{i-1} for
+//          i = 1 .. KP-2, the trailing c(KP-2, KP-1) at KP-1;
+//   T + j: tau_j as sm.tau[q][j] holds it, 0 for j = KP-2 and KP-1.
+// Lane l of a point's row reads words l, l + 16, ... of each half: a wave's four entries are
+// 4 WORDS contiguous words.
+template <int KP>
+struct FactorAux {
+  static constexpr int B = 0;
+  static constexpr int T = KP;
+  static constexpr int WORDS = 2 * KP;
+};
 hipError_t launch_assemble_record(hipStream_t s, int kp, const TreeDesc *trees, SolveConsts c,
                                   SlabDev slab, long long g0, int npts, const int *nbr_cnt,
                                   const int *nbr_idx, int2 *info, double *ws);
@@ -279,11 +293,13 @@ hipError_t launch_solve_tq40(hipStream_t s, int kp, SolveConsts c, SlabDev slab,
 // The record cache's pair (cwbl_tq40_fill.hip): fill_tq40_factor_kernel is solve_tq40_kernel's
 // analysis from the records `ws`, which it leaves as FactorRecords; solve_tq40_factor_kernel is
 // the same analysis from those.  Same launch contract as launch_solve_tq40 (the spare record
-// included).
+// included); aux: the FactorAux entries of the npts + 1 records `ws` (the fill writes those of
+// the npts points, the hit's lanes past the launch read the spare one).
 hipError_t launch_fill_tq40_factor(hipStream_t s, int kp, SolveConsts c, SlabDev slab,
-                                   long long g0, int npts, double *ws, int2 *info);
+                                   long long g0, int npts, double *ws, double *aux, int2 *info);
 hipError_t launch_solve_tq40_factor(hipStream_t s, int kp, SolveConsts c, SlabDev slab,
-                                    long long g0, int npts, const double *ws, int2 *info);
+                                    long long g0, int npts, const double *ws, const double *aux,
+                                    int2 *info);
 
 // cwbl_analyze_vars: the variables of a group share the record (A, b1) and so the factor
 // A = Q T Q^T; solve_tq40_multi_kernel (cwbl_tq40_multi.hip) tridiagonalises once per point

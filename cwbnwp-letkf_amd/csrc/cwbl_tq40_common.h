@@ -20,8 +20,8 @@
 // count and the var index re-read or recomputed at their uses):
 //   phase 1 and phase 2 of the tridiagonalisation   single (carries x' too, keeps x scal);
 //                                                   multi = column = fill (b1 only, keep x and
-//                                                   scal; fill also keeps each step's alpha)
-//   per-step dlarfg from the stored alpha and x     factor (xx: the steps' own chains)
+//                                                   scal; fill stores them with beta and tau,
+//                                                   factor loads them: no step of its own)
 //   quadrature level loop and LDS walk offsets      single = multi = column = fill/factor
 //   replay of the reflectors on x'                  multi = column = fill/factor
 //   quadrature round loop and d                     single = multi = column = fill/factor

@@ -4,13 +4,14 @@
 //   fill_tq40_factor_kernel<KP>   a cache fill: solve_tq40_multi_kernel's b1-only
 //                                 tridiagonalisation of the record, then the factor
 //                                 (FactorRecord, cwbl_internal.h) goes out over the record it
-//                                 came from, and the call's variable is solved from it;
+//                                 came from, the steps' beta and tau to the point's FactorAux
+//                                 entry, and the call's variable is solved from it;
 //   solve_tq40_factor_kernel<KP>  a cache hit: loads the factor where the multi kernel keeps
 //                                 its reflectors (phase 1: sm.pv, phase 2: the registers of the
-//                                 columns they eliminated), recomputes every step's beta, tau
-//                                 and scal with the same dlarfg(alpha, xx), and solves the
-//                                 call's variable.  No O(k^3) work: the kernel streams 6880 B
-//                                 per point.
+//                                 columns they eliminated) and T's off-diagonal and the taus
+//                                 where it keeps those (sm.tq, sm.tau), and solves the call's
+//                                 variable.  No O(k^3) work and no dlarfg: the kernel streams
+//                                 6880 + 640 B per point.
 //
 // The factor is a function of the record alone, and both kernels run the same text
 // (tq40_factor_solve) on it: the multi kernel's replay of the reflectors on x', then the
@@ -18,16 +19,15 @@
 // epilogue.  Every floating-point expression is one solve_tq40_kernel evaluates on the same
 // bits, so a fill or a hit equals solve_tq40_kernel on the record bit for bit:
 //   - x is kept unscaled and masked (0 on the rows <= j + 1 and >= k), as the step formed it;
-//   - xx is the step's chain over the same x (phase 1: xP xP, then fma(x_r, x_r, xx); phase 2:
-//     from 0.0 under the same slot guards) and the same row sum (rsum16xN documents rsum16's
-//     rounding order).  The xx of different steps do not depend on each other, so the hit
-//     kernel sums them several steps at a time, before the replay, instead of one per step
-//     beside x . x';
-//   - alpha_j = A(j + 1, j) is stored as step j's dlarfg read it, so beta, tau, scal repeat.
+//   - beta, tau and scal are kept as the step's dlarfg returned them (its xx == 0 branch and
+//     NaNs included): the hit stores what it loaded, nothing is derived again.  scal lies at
+//     row j + 1 of the factor's column j, which is the lane (phase 2) or, the column's first
+//     word, the address (phase 1) that the replay reads it from.
 //
 // In place: a wave is the only reader of its four records and has loaded them entirely
 // (tq40_load_record; every loaded word feeds step 0) before the factor's first store; lanes
-// past npts only ever read the spare record and store nothing.
+// past npts only ever read the spare record and store nothing.  The FactorAux entries are a
+// buffer of their own: plain stores from the valid lanes.
 #include "cwbl_tq40_common.h"
 
 #include <utility>
@@ -36,7 +36,7 @@ namespace cwbl {
 
 namespace {
 
-// Two row sums (the steps' x.x and x.b1: rsum16x3 without the x' sum)
+// Two row sums (the fill's steps' x.x and x.b1: rsum16x3 without the x' sum)
 __device__ __forceinline__ void rsum16x2(double &a, double &b) {
   double ab[2] = {a, b};
   rsum16xN(ab);
@@ -398,9 +398,11 @@ __device__ __forceinline__ void tq40_factor_solve(
 template <int KP>
 __global__ void __launch_bounds__(64, 2)
 fill_tq40_factor_kernel(SolveConsts c, SlabDev slab, long long g0, int npts,
-                        double *__restrict__ ws, int2 *__restrict__ info) {
+                        double *__restrict__ ws, double *__restrict__ aux,
+                        int2 *__restrict__ info) {
   using LY = Tq40Layout<KP>;
   using FR = FactorRecord<KP>;
+  using FA = FactorAux<KP>;
   constexpr int J0 = LY::J0, KT = LY::KT, NS = LY::NS;
   using SM = Tq40Smem<KP>;
   __shared__ SM sm;
@@ -421,8 +423,7 @@ fill_tq40_factor_kernel(SolveConsts c, SlabDev slab, long long g0, int npts,
   tq40_load_record<KP>(ws, g4, q, l, valid, npts, A, Pb, ubP, ub);
 
   // ---- phase 1: Householder steps 0 .. J0-1 with the prefix block (b1 only) ---------------
-  // (twin: solve_tq40_multi_kernel's phase 1 and phase 2; this kernel's own: each step's alpha
-  // goes to the (Q^T x') word of sm.tq, which is idle until the replay)
+  // (twin: solve_tq40_multi_kernel's phase 1 and phase 2)
   sfor<J0>([&](auto jj) {
     constexpr int j = decltype(jj)::value, J1 = j + 1;
     const double dj = rbcast<j>(Pb[j]);  // A(j,j): final diagonal of T
@@ -457,7 +458,6 @@ fill_tq40_factor_kernel(SolveConsts c, SlabDev slab, long long g0, int npts,
     // every lane of the row writes the same value (no divergent branch in the step)
     sm.tq[q][j][0] = dj;
     sm.tq[q][J1][1] = h.beta;
-    sm.tq[q][j][3] = alpha;
     sm.tau[q][j] = h.tau;
     const double tau = h.tau;
     // v: 1 at row j + 1, x * scal below
@@ -595,7 +595,6 @@ fill_tq40_factor_kernel(SolveConsts c, SlabDev slab, long long g0, int npts,
       const double tau = h.tau;
       sm.tq[q][j][0] = dj;
       sm.tq[q][j + 1][1] = h.beta;
-      sm.tq[q][j][3] = alpha;
       sm.tau[q][j] = tau;
       double v[NS];
       sfor<NS>([&](auto rr) {
@@ -693,33 +692,40 @@ fill_tq40_factor_kernel(SolveConsts c, SlabDev slab, long long g0, int npts,
       constexpr int r = decltype(rr)::value;
       st((unsigned)(FR::U1 + J0 + l + 16 * r), ub[r]);
     });
-    sfor<J0>([&](auto jj) {  // phase 1's columns: alpha at row j + 1, x below
+    sfor<J0>([&](auto jj) {  // phase 1's columns: scal (sm.pv's word 0) at row j + 1, x below
       constexpr int j = decltype(jj)::value, J1 = j + 1;
-      const double alpha = sm.tq[q][j][3];
       const double *pj = sm.pv[q][j];
-      if (pre && l >= J1) st((unsigned)(FR::col(j) + l - J1), l == J1 ? alpha : pj[l]);
+      if (pre && l >= J1) st((unsigned)(FR::col(j) + l - J1), pj[l == J1 ? 0 : l]);
       sfor<NS>([&](auto rr) {
         constexpr int r = decltype(rr)::value;
         const int i = J0 + l + 16 * r;
-        double xv = pj[i];
-        if constexpr (J1 == J0 && r == 0) xv = l == 0 ? alpha : xv;
-        st((unsigned)(FR::col(j) + i - J1), xv);
+        if constexpr (J1 == J0 && r == 0) st((unsigned)(FR::col(j) + i - J1), pj[l == 0 ? 0 : i]);
+        else st((unsigned)(FR::col(j) + i - J1), pj[i]);
       });
     });
-    sfor<KT - 2>([&](auto jj) {  // phase 2's columns
-      constexpr int jl = decltype(jj)::value, j = J0 + jl, J1 = jl + 1;
-      const double alpha = sm.tq[q][j][3];
+    sfor<KT - 2>([&](auto jj) {  // phase 2's columns, as the registers hold them: scal at row
+      constexpr int jl = decltype(jj)::value, j = J0 + jl, J1 = jl + 1;  // j + 1, x below
       sfor<NS>([&](auto rr) {
         constexpr int r = decltype(rr)::value;
         if constexpr (16 * r + 15 >= J1) {
           const int t = l + 16 * r;
-          double xv = alpha;
-          if constexpr (16 * r + 15 > J1) xv = t == J1 ? alpha : A[r][j];
-          if (t >= J1) st((unsigned)(FR::col(j) + t - J1), xv);
+          if (t >= J1) st((unsigned)(FR::col(j) + t - J1), A[r][j]);
         }
       });
     });
-    if (l == 0) st((unsigned)FR::EL, sm.tq[q][KP - 1][1]);
+    if (l == 0) st((unsigned)FR::EL, 0.0);  // (unused: every record word is replaced)
+    // the steps' beta and tau: the point's FactorAux
+    const unsigned ab = (unsigned)gi * (unsigned)FA::WORDS;
+    sfor<(KP + 15) / 16>([&](auto rr) {
+      constexpr int r = decltype(rr)::value;
+      const int i = l + 16 * r;
+      if (16 * r + 15 < KP || i < KP) {
+        gst(aux, 8u * (ab + (unsigned)(FA::B + i)), sm.tq[q][i][1]);
+        // (steps KP-2 and KP-1 do not exist: sm.tau has nothing there)
+        const double tj = sm.tau[q][i < KP - 2 ? i : 0];
+        gst(aux, 8u * (ab + (unsigned)(FA::T + i)), i < KP - 2 ? tj : 0.0);
+      }
+    });
   }
 
   tq40_factor_solve<KP>(c, slab, sm, A, g0, valid, ptot, gi, q, l, info);
@@ -729,9 +735,11 @@ fill_tq40_factor_kernel(SolveConsts c, SlabDev slab, long long g0, int npts,
 template <int KP>
 __global__ void __launch_bounds__(64, 2)
 solve_tq40_factor_kernel(SolveConsts c, SlabDev slab, long long g0, int npts,
-                         const double *__restrict__ ws, int2 *__restrict__ info) {
+                         const double *__restrict__ ws, const double *__restrict__ aux,
+                         int2 *__restrict__ info) {
   using LY = Tq40Layout<KP>;
   using FR = FactorRecord<KP>;
+  using FA = FactorAux<KP>;
   constexpr int J0 = LY::J0, KT = LY::KT, NS = LY::NS;
   using SM = Tq40Smem<KP>;
   __shared__ SM sm;
@@ -757,15 +765,28 @@ solve_tq40_factor_kernel(SolveConsts c, SlabDev slab, long long g0, int npts,
                                                         (int)(cb & ~4095u), 0);
     return __longlong_as_double(((long long)v[1] << 32) | (unsigned)v[0]);
   };
+  // the same from a byte offset, which may be kRecSkip: that lane loads 0 without an access
+  auto rwb = [&](unsigned vbyte, unsigned cword) {
+    const unsigned cb = 8u * cword;
+    const auto v = __builtin_amdgcn_raw_buffer_load_b64(rs, (int)(vbyte + (cb & 4095u)),
+                                                        (int)(cb & ~4095u), 0);
+    return __longlong_as_double(((long long)v[1] << 32) | (unsigned)v[0]);
+  };
   const unsigned rl = rq + (unsigned)l;
-  double A[NS][KP];     // phase 2's columns J0 .. KP-3 only: alpha at row j + 1, x below
-  double c1P[J0], c1[J0][NS];  // phase 1's columns
+  double A[NS][KP];     // phase 2's columns J0 .. KP-3 only: scal at row j + 1, x below, 0 above
+  // phase 1's columns: c1P is x on the prefix rows > j + 1 and the step's scal (the column's
+  // first word, row j + 1) on every other lane
+  double c1P[J0], c1[J0][NS];
   sfor<J0>([&](auto jj) {
     constexpr int j = decltype(jj)::value, J1 = j + 1;
-    c1P[j] = rw(rq + (unsigned)((pre && l >= J1) ? l - J1 : 0), (unsigned)FR::col(j));
+    c1P[j] = rw(rq + (unsigned)((pre && l > J1) ? l - J1 : 0), (unsigned)FR::col(j));
     sfor<NS>([&](auto rr) {
       constexpr int r = decltype(rr)::value;
-      c1[j][r] = rw(rl, (unsigned)(FR::col(j) + J0 + 16 * r - J1));
+      // (step J0-1: row j + 1 = J0 is lane 0 of slot 0, whose x is 0)
+      if constexpr (J1 == J0 && r == 0)
+        c1[j][r] = rwb(rec_off(l != 0, (int)rl), (unsigned)(FR::col(j) + J0 + 16 * r - J1));
+      else
+        c1[j][r] = rw(rl, (unsigned)(FR::col(j) + J0 + 16 * r - J1));
     });
   });
   sfor<KT - 2>([&](auto jj) {
@@ -774,9 +795,9 @@ solve_tq40_factor_kernel(SolveConsts c, SlabDev slab, long long g0, int npts,
       constexpr int r = decltype(rr)::value;
       if constexpr (16 * r >= J1) {
         A[r][j] = rw(rl, (unsigned)(FR::col(j) + 16 * r - J1));
-      } else if constexpr (16 * r + 15 >= J1) {
+      } else if constexpr (16 * r + 15 >= J1) {  // the rows above j + 1 are 0
         const int t = l + 16 * r;
-        A[r][j] = rw(rq + (unsigned)(t >= J1 ? t - J1 : 0), (unsigned)FR::col(j));
+        A[r][j] = rwb(rec_off(t >= J1, (int)rq + t - J1), (unsigned)FR::col(j));
       }
     });
   });
@@ -795,9 +816,26 @@ solve_tq40_factor_kernel(SolveConsts c, SlabDev slab, long long g0, int npts,
     constexpr int r = decltype(rr)::value;
     ub[r] = rw(rl, (unsigned)(FR::U1 + J0 + 16 * r));
   });
-  const double el = rw(rq, (unsigned)FR::EL);
+  // the steps' beta and tau: the wave's four FactorAux entries, the same way (the spare entry
+  // for a lane past the batch).  Lane l takes words l, l + 16 and, l < 8, l + 32 of each half;
+  // the lanes >= 8 take word l + 16 again, and store it again below.
+  const __amdgpu_buffer_rsrc_t ra = rec_rsrc(aux + (size_t)(4 * g4) * FA::WORDS, 4 * FA::WORDS);
+  const unsigned aq = (unsigned)(valid ? q : npts - 4 * g4) * (unsigned)FA::WORDS;
+  constexpr int NA = (KP + 15) / 16;
+  static_assert(16 * (NA - 1) + 8 == KP, "the last run of an aux half is half a row");
+  const int l2 = l < 8 ? l + 16 * (NA - 1) : l + 16 * (NA - 2);
+  auto arow = [&](int r) { return r < NA - 1 ? l + 16 * r : l2; };
+  double bt[NA], ta[NA];
+  sfor<NA>([&](auto rr) {
+    constexpr int r = decltype(rr)::value;
+    const unsigned off = 8u * (aq + (unsigned)arow(r));
+    const auto vb = __builtin_amdgcn_raw_buffer_load_b64(ra, (int)(off + 8u * FA::B), 0, 0);
+    const auto vt = __builtin_amdgcn_raw_buffer_load_b64(ra, (int)(off + 8u * FA::T), 0, 0);
+    bt[r] = __longlong_as_double(((long long)vb[1] << 32) | (unsigned)vb[0]);
+    ta[r] = __longlong_as_double(((long long)vt[1] << 32) | (unsigned)vt[0]);
+  });
 
-  // ---- T's diagonal, Q^T b1 and the trailing off-diagonal -------------------------------------
+  // ---- T's diagonal and off-diagonal, Q^T b1 and the steps' tau ---------------------------------
   sfor<(KP + 15) / 16>([&](auto rr) {
     constexpr int r = decltype(rr)::value;
     const int i = l + 16 * r;
@@ -808,77 +846,25 @@ solve_tq40_factor_kernel(SolveConsts c, SlabDev slab, long long g0, int npts,
     constexpr int r = decltype(rr)::value;
     sm.tq[q][J0 + l + 16 * r][2] = ub[r];
   });
-  // (every lane of the row stores the same values: no branch among the loads)
-  sm.tq[q][0][1] = 0.0;
-  sm.tq[q][KP][1] = 0.0;
-  sm.tq[q][KP - 1][1] = el;
+  // T's off-diagonal (word 0 is 0, word KP-1 the trailing 2 x 2's) and tau as the fill's steps
+  // left them in LDS; row KP's off-diagonal closes the walk from the bottom
+  sfor<NA>([&](auto rr) {
+    constexpr int r = decltype(rr)::value;
+    sm.tq[q][arow(r)][1] = bt[r];
+    sm.tau[q][arow(r)] = ta[r];
+  });
+  sm.tq[q][KP][1] = 0.0;  // (every lane of the row stores the same value: no branch)
 
-  // ---- every step's dlarfg again: beta, tau, scal from the stored alpha and x -----------------
-  // phase 1's steps: xx = xP xP, then fma(x_r, x_r, xx) (solve_tq40_kernel's chain), all J0 row
-  // sums at once
-  {
-    double xP[J0], xx[J0];
-    sfor<J0>([&](auto jj) {
-      constexpr int j = decltype(jj)::value, J1 = j + 1;
-      xP[j] = (pre && l > J1) ? c1P[j] : 0.0;
-      xx[j] = xP[j] * xP[j];
-      sfor<NS>([&](auto rr) {
-        constexpr int r = decltype(rr)::value;
-        double x = c1[j][r];
-        if constexpr (J1 == J0 && r == 0) x = l == 0 ? 0.0 : x;  // row j + 1 holds alpha
-        xx[j] = fma(x, x, xx[j]);
-      });
-    });
-    rsum16xN(xx);
-    sfor<J0>([&](auto jj) {
-      constexpr int j = decltype(jj)::value, J1 = j + 1;
-      double alpha;
-      if constexpr (J1 < J0) alpha = rbcast<J1>(c1P[j]);
-      else alpha = rbcast<0>(c1[j][0]);
-      const Refl h = dlarfg(alpha, xx[j]);
-      sm.tq[q][J1][1] = h.beta;
-      sm.tau[q][j] = h.tau;
-      // sm.pv[q][j] as solve_tq40_multi_kernel leaves it: x by row, word 1 the dump word of
-      // the lanes whose x is 0, then the step's scal in word 0
-      sm.pv[q][j][(pre && l > 1) ? l : 1] = xP[j];
-      sfor<NS>([&](auto rr) {
-        constexpr int r = decltype(rr)::value;
-        double x = c1[j][r];
-        if constexpr (J1 == J0 && r == 0) x = l == 0 ? 0.0 : x;
-        sm.pv[q][j][J0 + l + 16 * r] = x;
-      });
-      sm.pv[q][j][0] = h.scal;
-    });
-  }
-  // phase 2's steps, kFG row sums at a time: xx from 0.0 under the slots' guards
-  constexpr int kFG = 6;
-  static_assert((KT - 2) % kFG == 0, "phase 2's steps in whole groups");
-  sfor<(KT - 2) / kFG>([&](auto gg) {
-    constexpr int jl0 = kFG * decltype(gg)::value;
-    double xx[kFG], alpha[kFG];
-    sfor<kFG>([&](auto ee) {
-      constexpr int e = decltype(ee)::value, jl = jl0 + e, j = J0 + jl;
-      constexpr int J1 = jl + 1, R1 = J1 / 16, L1 = J1 % 16;
-      alpha[e] = rbcast<L1>(A[R1][j]);
-      xx[e] = 0.0;
-      sfor<NS>([&](auto rr) {
-        constexpr int r = decltype(rr)::value;
-        if constexpr (16 * r + 15 > J1) {
-          const int t = l + 16 * r;
-          if constexpr (16 * r <= J1) A[r][j] = t > J1 ? A[r][j] : 0.0;  // x: 0 on rows <= j + 1
-          xx[e] = fma(A[r][j], A[r][j], xx[e]);
-        }
-      });
-    });
-    rsum16xN(xx);
-    sfor<kFG>([&](auto ee) {
-      constexpr int e = decltype(ee)::value, jl = jl0 + e, j = J0 + jl;
-      constexpr int J1 = jl + 1, R1 = J1 / 16;
-      const Refl h = dlarfg(alpha[e], xx[e]);
-      sm.tq[q][j + 1][1] = h.beta;
-      sm.tau[q][j] = h.tau;
-      // the step's scal takes row j + 1 of its column (solve_tq40_multi_kernel's layout)
-      A[R1][j] = l + 16 * R1 == J1 ? h.scal : (16 * R1 + 15 > J1 ? A[R1][j] : 0.0);
+  // ---- the reflectors, where solve_tq40_multi_kernel keeps them -----------------------------------
+  // phase 1: sm.pv[q][j] holds x by row and the step's scal in word 0, which the lanes without
+  // a prefix row of x store (the same value from each); phase 2's columns are in place as
+  // loaded
+  sfor<J0>([&](auto jj) {
+    constexpr int j = decltype(jj)::value, J1 = j + 1;
+    sm.pv[q][j][(pre && l > J1) ? l : 0] = c1P[j];
+    sfor<NS>([&](auto rr) {
+      constexpr int r = decltype(rr)::value;
+      sm.pv[q][j][J0 + l + 16 * r] = c1[j][r];
     });
   });
   __syncthreads();
@@ -887,22 +873,23 @@ solve_tq40_factor_kernel(SolveConsts c, SlabDev slab, long long g0, int npts,
 }
 
 hipError_t launch_fill_tq40_factor(hipStream_t s, int kp, SolveConsts c, SlabDev slab,
-                                   long long g0, int npts, double *ws, int2 *info) {
+                                   long long g0, int npts, double *ws, double *aux, int2 *info) {
   if (npts <= 0) return hipSuccess;
-  if (c.quad_r == nullptr || kp != kTq4KP) return hipErrorInvalidValue;
+  if (c.quad_r == nullptr || aux == nullptr || kp != kTq4KP) return hipErrorInvalidValue;
   const dim3 grid((npts + 3) / 4);
   hipLaunchKernelGGL((fill_tq40_factor_kernel<kTq4KP>), grid, dim3(64), 0, s, c, slab, g0, npts,
-                     ws, info);
+                     ws, aux, info);
   return hipGetLastError();
 }
 
 hipError_t launch_solve_tq40_factor(hipStream_t s, int kp, SolveConsts c, SlabDev slab,
-                                    long long g0, int npts, const double *ws, int2 *info) {
+                                    long long g0, int npts, const double *ws, const double *aux,
+                                    int2 *info) {
   if (npts <= 0) return hipSuccess;
-  if (c.quad_r == nullptr || kp != kTq4KP) return hipErrorInvalidValue;
+  if (c.quad_r == nullptr || aux == nullptr || kp != kTq4KP) return hipErrorInvalidValue;
   const dim3 grid((npts + 3) / 4);
   hipLaunchKernelGGL((solve_tq40_factor_kernel<kTq4KP>), grid, dim3(64), 0, s, c, slab, g0, npts,
-                     ws, info);
+                     ws, aux, info);
   return hipGetLastError();
 }
 

@@ -384,13 +384,16 @@ enum {
                                 * automatic, default: all levels of the column unless the
                                 * columns alone do not fill the device).  The result does not
                                 * depend on it; tests use it to force level splits */
-  CWBL_OPT_FACTOR_REUSE = 17   /* what CWBL_OPT_RECORD_REUSE keeps of a point, in the same
-                                * 6880 bytes: 1 (default) the factor A = Q T Q^T of the record,
-                                * written over it by the call that fills the cache, so a later
-                                * call with an equal key skips the tridiagonalisation as well;
-                                * 0 the assembled record itself, tridiagonalised again by every
-                                * call.  Bit-identical results either way; budget, key,
-                                * counters and cwbl_reuse_info do not depend on it */
+  CWBL_OPT_FACTOR_REUSE = 17   /* what CWBL_OPT_RECORD_REUSE keeps of a point: 1 (default) the
+                                * factor A = Q T Q^T of the record, written over its 6880 bytes
+                                * by the call that fills the cache, and 640 bytes more with the
+                                * reduction's step scalars, so a later call with an equal key
+                                * skips the tridiagonalisation as well; 0 the assembled record
+                                * itself, tridiagonalised again by every call.  Bit-identical
+                                * results either way.  The budget bounds the 6880-byte part
+                                * alone, so the cached batches, the key, the counters and
+                                * cwbl_reuse_info's batch counts do not depend on it; its
+                                * bytes_held includes the 640-byte part */
 };
 int         cwbl_set_option(int option, long long value);
 
@@ -434,8 +437,8 @@ int         cwbl_prep_info(cwbl_prep_info_t *out);
 typedef struct cwbl_reuse_info_t {
   long long batches_reused;     /* search batches solved from kept records */
   long long batches_assembled;  /* search batches that ran the search and the assembly */
-  long long bytes_held;         /* device memory of the cache: records, accepted counts and
-                                 * the coordinate snapshot */
+  long long bytes_held;         /* device memory of the cache: records (or factors and their
+                                 * step scalars), accepted counts and the coordinate snapshot */
   double    ms_compare;         /* host time of the coordinate compare, its read-back and
                                  * synchronisation included (0: the key already differed) */
 } cwbl_reuse_info_t;
