@@ -55,15 +55,37 @@ __device__ __forceinline__ long long touched(long long x) {
   return x;
 }
 
+// The background gathers of a point, as loaded: member i = row i.  Branch-free, every address
+// valid: a lane past the batch reads member 0 of point 0, a row past k member 0 of its point
+// (tq40_factor_solve masks both to 0).  The hit issues these inside the factor's stream, so
+// that the two HBM latencies overlap; the fill, whose registers are full until its factor is
+// stored, just before the solve.
+template <int KP>
+__device__ __forceinline__ void tq40_load_xb(const SlabDev &slab, const long long g0,
+                                             const bool valid, const int gi, const int l,
+                                             const int k, float (&xv)[Tq40Layout<KP>::NV]) {
+  const float *__restrict__ const var = slab.var;
+  const long long P = tq40_var_index(slab, g0, valid ? gi : 0);  // var index of member 0
+  sfor<Tq40Layout<KP>::NV>([&](auto vv) {
+    constexpr int vs = decltype(vv)::value;
+    const int i = tq40_vrow<KP>(l, vs);
+    xv[vs] = var[P + slab.L * ((valid && i < k) ? i : 0)];
+  });
+}
+
 // The call's variable from a point's factor.  On entry (after a barrier): sm.tq[q][i][0..2]
 // hold d_i, c(i-1, i) and (Q^T b1)_i, sm.tau the steps' tau, sm.pv[q][j] phase 1's x with the
 // step's scal in word 0, A[r][j] (j >= J0) phase 2's x with the step's scal at row j + 1.
 // (Twin: solve_tq40_multi_kernel's variable loop body, with the flags
 // and alphas of SolveConsts and slab.var.)
-template <int KP>
+// AHEAD (the hit) changes the order of loads only, never an expression: the first round's
+// node is fetched before the replay and each later one a round ahead, and the walk reads row
+// t + 1 before d_{t-1}'s reciprocal.  That costs six VGPRs, which the fill does not have.
+template <int KP, bool AHEAD>
 __device__ __forceinline__ void tq40_factor_solve(
     const SolveConsts &c, const SlabDev &slab, Tq40Smem<KP> &sm,
-    double (&A)[Tq40Layout<KP>::NS][KP], const long long g0, const bool valid, const int ptot, const int gi, const int q, const int l,
+    double (&A)[Tq40Layout<KP>::NS][KP], const float (&xbv)[Tq40Layout<KP>::NV], const long long g0,
+    const bool valid, const int ptot, const int gi, const int q, const int l,
     int2 *__restrict__ info) {
   using LY = Tq40Layout<KP>;
   constexpr int J0 = LY::J0, KT = LY::KT, NS = LY::NS, NV = LY::NV, H = LY::H;
@@ -91,6 +113,8 @@ __device__ __forceinline__ void tq40_factor_solve(
   const int R = tq40_wave_rounds(level);
   const int NQ = 8 * R - 1;  // (R is wave-uniform)
   const double2 *qtab = quad_rule(c.quad_r, R, level);
+  double2 twn;  // AHEAD: the next round's node, in flight
+  if constexpr (AHEAD) twn = qtab[min(l & 7, NQ - 1)];
   const int side = l >> 3, n8 = l & 7;
   const double(*T)[4] = sm.tq[q];
   char *const smb = reinterpret_cast<char *>(&sm);
@@ -122,17 +146,14 @@ __device__ __forceinline__ void tq40_factor_solve(
   const int use_rtpp = c.use_rtpp, use_rtps = c.use_rtps;
   const float rtpp_alpha = c.rtpp_alpha, rtps_alpha = c.rtps_alpha;
 
-  // background of the point: member i = row i
+  // background of the point: member i = row i (xbv: tq40_load_xb's gathers)
   float xbl[NV];
   double xb_mean;
   {
-    const long long P = tq40_var_index(slab, g0, valid ? gi : 0);  // var index of member 0
     sfor<NV>([&](auto vv) {
       constexpr int vs = decltype(vv)::value;
-      const int i = vrow(vs);
-      const bool mem = valid && i < k;
-      const float xv = var[P + slab.L * (mem ? i : 0)];  // branch-free: a valid address
-      xbl[vs] = mem ? xv : 0.0f;
+      const bool mem = valid && vrow(vs) < k;
+      xbl[vs] = mem ? xbv[vs] : 0.0f;
     });
     // sum(xb) * nmember_inv (:671)
     xb_mean = (double)(seq_sum_f32<KP>(xbl) * c.nmember_inv);
@@ -145,7 +166,6 @@ __device__ __forceinline__ void tq40_factor_solve(
     ux[r] = t < k ? (double)xbl[r + 1] - xb_mean : 0.0;
   });
 
-  touch_cols();
   // ---- replay: x' <- Q^T x', the x' half of every step of solve_tq40_kernel ----------------
   sfor<J0>([&](auto jj) {  // phase 1's reflectors
     constexpr int j = decltype(jj)::value, J1 = j + 1;
@@ -178,6 +198,11 @@ __device__ __forceinline__ void tq40_factor_solve(
   sfor<KT - 2>([&](auto jj) {  // phase 2's reflectors
     constexpr int jl = decltype(jj)::value, j = J0 + jl;
     constexpr int J1 = jl + 1, R1 = J1 / 16, L1 = J1 % 16;
+    // (touch_cols, column by column: on a hit the column may still be in flight until here)
+    sfor<NS>([&](auto rr) {
+      constexpr int r = decltype(rr)::value;
+      if constexpr (16 * r + 15 > J1 || r == R1) touch(A[r][j]);
+    });
     const double scal = rbcast<L1>(A[R1][j]), tau = sm.tau[q][j];
     double x[NS], xu = 0.0;
     sfor<NS>([&](auto rr) {
@@ -213,24 +238,48 @@ __device__ __forceinline__ void tq40_factor_solve(
   sfor<NV>([&](auto vv) { ys[decltype(vv)::value] = 0.0; });
   for (int round = 0; round < R; ++round) {
     const int node = 8 * round + n8;
-    const double2 tw = qtab[min(node, NQ - 1)];
+    double2 tw;
+    if constexpr (AHEAD) {
+      tw = twn;
+      // the next round's node, one round ahead (R is wave-uniform: no divergence)
+      if (round + 1 < R) twn = qtab[min(node + 8, NQ - 1)];
+    } else {
+      tw = qtab[min(node, NQ - 1)];
+    }
     const double sigma = node < NQ ? m * tw.x : 0.0;
     const double omega = node < NQ ? sqrt(m) * tw.y : 1.0;
     double hh[H], mm[H];
     unsigned pw = tq0;
     double dl = lds(pw) + sigma, gt = lds(pw + 24);
-    double rdl = rcp64(dl);
+    // The next row's three words, read once d_{t-1} is known (the empty asm: read earlier,
+    // all H rows would be live at once).  AHEAD reads row t + 1 there, before d_{t-1}'s
+    // reciprocal, so that the LDS round trip runs under the rcp64 chain (rows 1 .. H-1 only:
+    // never past the walk); otherwise it is row t, one register triple less.
+    double nd, nc, ng;
+    auto next_row = [&]() {
+      pw += dirb;
+      nd = lds(pw);
+      nc = lds(pw + csb);
+      ng = lds(pw + 24);
+    };
+    if constexpr (AHEAD) next_row();
     sfor<H - 1>([&](auto tt) {
       constexpr int t = decltype(tt)::value + 1;
-      pw += dirb;
-      asm volatile("" : "+v"(pw) : "v"(dl));  // row t is read once d_{t-1} is known
-      const double ct = lds(pw + csb);
+      if constexpr (!AHEAD) {
+        asm volatile("" : "+v"(pw) : "v"(dl));
+        next_row();
+      }
+      const double dt = nd, ct = nc, g = ng;
+      if constexpr (AHEAD && t < H - 1) {
+        asm volatile("" : "+v"(pw) : "v"(dl));
+        next_row();
+      }
+      const double rdl = rcp64(dl);
       const double lt = ct * rdl;
       hh[t - 1] = gt * rdl;
       mm[t - 1] = lt;
-      dl = fma(-lt, ct, lds(pw) + sigma);
-      gt = fma(-lt, gt, lds(pw + 24));
-      rdl = rcp64(dl);
+      dl = fma(-lt, ct, dt + sigma);
+      gt = fma(-lt, gt, g);
     });
     // rows H-1 (top) and H (bottom): 2x2 solve with the partner lane's pivot
     const double cm = T[H][1];
@@ -358,12 +407,18 @@ __device__ __forceinline__ void tq40_factor_solve(
       }
     });
     if (use_rtps) {
-      double d8 = 0.0;
+      // sum of xp^2 in member order: the squares per lane (the products of the broadcast
+      // values, formed once), then one fused row add each (x 1.0: the add's one rounding)
+      double d8 = 0.0, sq8[NV];
+      sfor<NV>([&](auto vv) {
+        constexpr int vs = decltype(vv)::value;
+        sq8[vs] = xpl[vs] * xpl[vs];  // 0 past member k-1
+        dpp_pin(sq8[vs]);
+      });
       sfor<KP>([&](auto mm) {
         constexpr int mb = decltype(mm)::value;
         constexpr int vs = mb < J0 ? 0 : 1 + (mb - J0) / 16, ln = mb < J0 ? mb : (mb - J0) % 16;
-        const double xp = rbcast<ln>(xpl[vs]);  // 0 past member k-1
-        d8 = d8 + xp * xp;
+        d8 = fmac_row<ln>(d8, sq8[vs], 1.0);
       });
       const float xb_std = (float)d8;
       float sq[NV];
@@ -728,7 +783,9 @@ fill_tq40_factor_kernel(SolveConsts c, SlabDev slab, long long g0, int npts,
     });
   }
 
-  tq40_factor_solve<KP>(c, slab, sm, A, g0, valid, ptot, gi, q, l, info);
+  float xv[LY::NV];
+  tq40_load_xb<KP>(slab, g0, valid, gi, l, k, xv);
+  tq40_factor_solve<KP, false>(c, slab, sm, A, xv, g0, valid, ptot, gi, q, l, info);
 }
 
 // ---- the hit: the call's variable from the kept factor -----------------------------------------
@@ -773,34 +830,9 @@ solve_tq40_factor_kernel(SolveConsts c, SlabDev slab, long long g0, int npts,
     return __longlong_as_double(((long long)v[1] << 32) | (unsigned)v[0]);
   };
   const unsigned rl = rq + (unsigned)l;
-  double A[NS][KP];     // phase 2's columns J0 .. KP-3 only: scal at row j + 1, x below, 0 above
-  // phase 1's columns: c1P is x on the prefix rows > j + 1 and the step's scal (the column's
-  // first word, row j + 1) on every other lane
-  double c1P[J0], c1[J0][NS];
-  sfor<J0>([&](auto jj) {
-    constexpr int j = decltype(jj)::value, J1 = j + 1;
-    c1P[j] = rw(rq + (unsigned)((pre && l > J1) ? l - J1 : 0), (unsigned)FR::col(j));
-    sfor<NS>([&](auto rr) {
-      constexpr int r = decltype(rr)::value;
-      // (step J0-1: row j + 1 = J0 is lane 0 of slot 0, whose x is 0)
-      if constexpr (J1 == J0 && r == 0)
-        c1[j][r] = rwb(rec_off(l != 0, (int)rl), (unsigned)(FR::col(j) + J0 + 16 * r - J1));
-      else
-        c1[j][r] = rw(rl, (unsigned)(FR::col(j) + J0 + 16 * r - J1));
-    });
-  });
-  sfor<KT - 2>([&](auto jj) {
-    constexpr int jl = decltype(jj)::value, j = J0 + jl, J1 = jl + 1;
-    sfor<NS>([&](auto rr) {
-      constexpr int r = decltype(rr)::value;
-      if constexpr (16 * r >= J1) {
-        A[r][j] = rw(rl, (unsigned)(FR::col(j) + 16 * r - J1));
-      } else if constexpr (16 * r + 15 >= J1) {  // the rows above j + 1 are 0
-        const int t = l + 16 * r;
-        A[r][j] = rwb(rec_off(t >= J1, (int)rq + t - J1), (unsigned)FR::col(j));
-      }
-    });
-  });
+  // Loads return in order, so they go out in the order of their first use: T, Q^T b1 and the
+  // steps' scalars (the trace, the level and every replay step need them), then phase 1's
+  // columns, then phase 2's, which the replay's first J0 steps leave in flight.
   double dg[(KP + 15) / 16];
   sfor<(KP + 15) / 16>([&](auto rr) {
     constexpr int r = decltype(rr)::value;
@@ -833,6 +865,39 @@ solve_tq40_factor_kernel(SolveConsts c, SlabDev slab, long long g0, int npts,
     const auto vt = __builtin_amdgcn_raw_buffer_load_b64(ra, (int)(off + 8u * FA::T), 0, 0);
     bt[r] = __longlong_as_double(((long long)vb[1] << 32) | (unsigned)vb[0]);
     ta[r] = __longlong_as_double(((long long)vt[1] << 32) | (unsigned)vt[0]);
+  });
+  double A[NS][KP];     // phase 2's columns J0 .. KP-3 only: scal at row j + 1, x below, 0 above
+  // phase 1's columns: c1P is x on the prefix rows > j + 1 and the step's scal (the column's
+  // first word, row j + 1) on every other lane
+  double c1P[J0], c1[J0][NS];
+  sfor<J0>([&](auto jj) {
+    constexpr int j = decltype(jj)::value, J1 = j + 1;
+    c1P[j] = rw(rq + (unsigned)((pre && l > J1) ? l - J1 : 0), (unsigned)FR::col(j));
+    sfor<NS>([&](auto rr) {
+      constexpr int r = decltype(rr)::value;
+      // (step J0-1: row j + 1 = J0 is lane 0 of slot 0, whose x is 0)
+      if constexpr (J1 == J0 && r == 0)
+        c1[j][r] = rwb(rec_off(l != 0, (int)rl), (unsigned)(FR::col(j) + J0 + 16 * r - J1));
+      else
+        c1[j][r] = rw(rl, (unsigned)(FR::col(j) + J0 + 16 * r - J1));
+    });
+  });
+  // The background gathers ride in the same stream, so the wave pays one HBM latency, not two:
+  // behind everything the solve needs before them (their address arithmetic would hold the
+  // stream's first load back by a hundred instructions) and ahead of phase 2's columns.
+  float xv[LY::NV];
+  tq40_load_xb<KP>(slab, g0, valid, gi, l, c.k, xv);
+  sfor<KT - 2>([&](auto jj) {
+    constexpr int jl = decltype(jj)::value, j = J0 + jl, J1 = jl + 1;
+    sfor<NS>([&](auto rr) {
+      constexpr int r = decltype(rr)::value;
+      if constexpr (16 * r >= J1) {
+        A[r][j] = rw(rl, (unsigned)(FR::col(j) + 16 * r - J1));
+      } else if constexpr (16 * r + 15 >= J1) {  // the rows above j + 1 are 0
+        const int t = l + 16 * r;
+        A[r][j] = rwb(rec_off(t >= J1, (int)rq + t - J1), (unsigned)FR::col(j));
+      }
+    });
   });
 
   // ---- T's diagonal and off-diagonal, Q^T b1 and the steps' tau ---------------------------------
@@ -869,7 +934,7 @@ solve_tq40_factor_kernel(SolveConsts c, SlabDev slab, long long g0, int npts,
   });
   __syncthreads();
 
-  tq40_factor_solve<KP>(c, slab, sm, A, g0, valid, ptot, gi, q, l, info);
+  tq40_factor_solve<KP, true>(c, slab, sm, A, xv, g0, valid, ptot, gi, q, l, info);
 }
 
 hipError_t launch_fill_tq40_factor(hipStream_t s, int kp, SolveConsts c, SlabDev slab,
