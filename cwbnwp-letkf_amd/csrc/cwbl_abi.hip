@@ -340,6 +340,11 @@ struct State {
   unsigned long long gen = 0;     // bumped by cwbl_init, cwbl_set_obs and cwbl_set_option
   size_t reuse_budget = 0;        // CWBL_OPT_RECORD_REUSE in bytes (0: no reuse)
   bool factor_reuse = true;       // CWBL_OPT_FACTOR_REUSE: the cache keeps factors, not records
+  bool hit_merge = true;          // CWBL_OPT_HIT_MERGE: one hit launch per info window
+  // the segment tables of a call's merged hit launches (HitSeg): written by the host, one
+  // asynchronous copy per launch
+  DevBuf hitseg;
+  PinBuf hitseg_pin;
   int column_share = 0;           // CWBL_OPT_COLUMN_SHARE: 0 off, 1 column kernel, 2 chunks only
   int column_levels = 0;          // CWBL_OPT_COLUMN_LEVELS: levels per wave (0: automatic)
   int ncu = 0;                    // compute units of the device (automatic level split)
@@ -938,9 +943,10 @@ void release_all() {
                     &S.sy, &S.salt, &S.svar, &S.bcol, &S.byo, &S.byb, &S.bxb, &S.bxa, &S.bev, &S.btri,
                     &S.qxyz, &S.qnf, &S.qidx, &S.qr2, &S.quad, &S.wsa, &S.flags, &S.tdesc_tree,
                     &S.ix_keys[0], &S.ix_keys[1], &S.ix_vals[0], &S.ix_vals[1], &S.ix_hist,
-                    &S.ix_part})
+                    &S.ix_part, &S.hitseg})
     b->release();
   S.ix_pin.release();
+  S.hitseg_pin.release();
   S.cache.release();
   for (hipEvent_t e : S.pevents) (void)hipEventDestroy(e);
   S.pevents.clear();
@@ -1056,6 +1062,10 @@ struct VarCall {
   int reuse = 0;
   long long ncached = 0;
   bool full_hit = false;
+  // CWBL_OPT_HIT_MERGE: the call's cached batches go out in one launch per info window;
+  // hitseg_used: entries of S.hitseg_pin taken by the launches so far
+  bool merge = false;
+  size_t hitseg_used = 0;
   // CWBL_OPT_COLUMN_SHARE (1 or 2 when the call is shared, else 0): sd is the column view of
   // the slab (nz = 1; L stays the member stride nx ny nz) and npts its ncol = ix_lim iy_lim
   // points, so the plan, the searches, the lists, the assembly and the info windows are per
@@ -1418,7 +1428,10 @@ int search_batch(VarCall &v, long long bi, int *ncnt, int *nidx, hipEvent_t a, h
   DevStats *dst = S.stats.as<DevStats>();
   // (timing experiment: CWBL_DEBUG_SERIAL=1 runs the searches on the solve stream)
   hipStream_t ss = S.serial_search ? S.stream : S.sstream;
-  if (bi >= 2) HIPCHK(hipStreamWaitEvent(ss, S.events[v.done_ev[bi - 2]], 0));
+  // (no event yet: the search of the first batch past the cached ones, queued ahead of the
+  // merged hit launch that covers batch bi - 2, which reads no lists)
+  if (bi >= 2 && bi - 2 < (long long)v.done_ev.size())
+    HIPCHK(hipStreamWaitEvent(ss, S.events[v.done_ev[bi - 2]], 0));
   HIPCHK(hipEventRecord(a, ss));
   int kt;
   if (S.binned) {
@@ -1935,6 +1948,7 @@ int cwbl_init(const cwbl_init_params *p) {
   S.column_share = 0;
   S.column_levels = 0;
   S.factor_reuse = true;
+  S.hit_merge = true;
   S.ncu = prop.multiProcessorCount;
   std::memset(&P, 0, sizeof P);
   std::memset(&CI, 0, sizeof CI);
@@ -1955,6 +1969,14 @@ int cwbl_init(const cwbl_init_params *p) {
 int cwbl_set_option(int option, long long value) {
   if (!S.inited) return fail(CWBL_ERR_STATE, "cwbl_set_option before cwbl_init");
   auto range = [&](long long lo, long long hi) { return value >= lo && value <= hi; };
+  if (option == CWBL_OPT_HIT_MERGE) {
+    // how the cached batches are launched, not what is cached: the generation stays
+    if (!range(0, 1))
+      return fail(CWBL_ERR_ARG, "cwbl_set_option: value %lld out of range for option %d", value,
+                  option);
+    S.hit_merge = value == 1;
+    return CWBL_OK;
+  }
   ++S.gen;  // options change the neighbour order and the batch plan: kept records are void
   switch (option) {
     case CWBL_OPT_SOLVER:
@@ -2184,6 +2206,70 @@ static int begin_call(const cwbl_slab *sl) {
   return CWBL_OK;
 }
 
+// CWBL_OPT_HIT_MERGE.  A call that hits has no search for a solve to overlap, so its cached
+// batches need not be launched one by one: each launch pays a ramp, a drain tail in which
+// every wave slot idles from its last wave's end to the slowest wave's, and the boundary
+// with its events (profiles/hit_merge.txt).  The segments of a cached batch are what
+// solve_batch_path launches for it: the batch, or its sub-batches under CWBL_OPT_SPLIT40_BATCH.
+static long long hit_segments(int nb, long long *Bs_out = nullptr) {
+  const long long cap = std::min<long long>(S.tq4_sub > 0 ? S.tq4_sub : nb, 1 << 19);
+  const long long Bs = std::min<long long>(sub_batch(nb, cap), 1 << 19);
+  if (Bs_out) *Bs_out = Bs;
+  return Bs >= nb ? 1 : (nb + Bs - 1) / Bs;
+}
+
+// Whether the call's cached batches go out merged, and room for their segment tables.
+static int plan_hit_merge(VarCall &v) {
+  v.merge = S.hit_merge && v.reuse == 2 && S.factor_reuse && !v.group && !v.colshare &&
+            !v.piped && !v.piped_back && !v.bounce && v.ncached > 0;
+  if (!v.merge) return CWBL_OK;
+  long long nseg = 0;
+  for (long long bi = 0; bi < v.ncached; ++bi) nseg += hit_segments(v.plan[bi].second);
+  if (nseg > 65535) {  // (a grid's rows; one launch may have to hold them all)
+    v.merge = false;
+    return CWBL_OK;
+  }
+  // grow-only: nothing is allocated from the second hit of a slab on
+  HIPCHK(S.hitseg.ensure((size_t)nseg * sizeof(HitSeg)));
+  HIPCHK(S.hitseg_pin.ensure((size_t)nseg * sizeof(HitSeg)));
+  return CWBL_OK;
+}
+
+// The hits of the cached batches [b0, b1), which lie in the open info window, in one launch
+// between the events b2 and dn.  Their segments go up ahead of b2, from page-locked memory
+// that the call writes once (each launch its own entries), into a table that only grows.
+static int solve_hits_merged(VarCall &v, long long b0, long long b1, hipEvent_t b2,
+                             hipEvent_t dn) {
+  RecordCache &C = S.cache;
+  HitSeg *const hseg = S.hitseg_pin.as<HitSeg>() + v.hitseg_used;
+  int nseg = 0, maxns = 0;
+  long long pts = 0;
+  for (long long bi = b0; bi < b1; ++bi) {
+    const long long g0 = v.plan[bi].first;
+    const int nb = v.plan[bi].second;
+    const long long ord = (long long)(C.off[bi] / AsmRecord<kTq4KP>::WORDS);
+    long long Bs;
+    hit_segments(nb, &Bs);
+    for (long long s0 = 0; s0 < nb; s0 += Bs) {
+      const int ns = (int)std::min<long long>(Bs, nb - s0);
+      hseg[nseg++] = HitSeg{g0 + s0, ord + s0, ns, (int)(g0 + s0 - v.win0)};
+      maxns = std::max(maxns, ns);
+    }
+    pts += nb;
+  }
+  HitSeg *const dseg = S.hitseg.as<HitSeg>() + v.hitseg_used;
+  HIPCHK(hipMemcpyAsync(dseg, hseg, (size_t)nseg * sizeof(HitSeg), hipMemcpyHostToDevice,
+                        S.stream));
+  v.hitseg_used += (size_t)nseg;
+  HIPCHK(hipEventRecord(b2, S.stream));
+  if (S.ktiming) S.kpend.push_back({KT_SOLVE_TQ40_FACTOR, b2, dn, pts});
+  HIPCHK(launch_solve_tq40_factor_merged(S.stream, S.kp, v.c, v.sd, dseg, nseg, maxns,
+                                         C.rec.as<double>(), C.aux.as<double>(),
+                                         S.info.as<int2>()));
+  HIPCHK(hipEventRecord(dn, S.stream));
+  return CWBL_OK;
+}
+
 // The driver of cwbl_analyze_var and of the group calls of cwbl_analyze_vars (v.vp, v.sl, and
 // for a group v.nvar, v.group and the flags of v.tv are the caller's; the arguments are
 // checked).  A group call runs with record reuse off: the cache is not read, filled or
@@ -2292,6 +2378,7 @@ static int analyze_call(VarCall &v, cwbl_stats *stats) {
   if (int rc = alloc_call_buffers(v)) return rc;
   if (reuse_on && v.reuse != 2)
     if (int rc = begin_fill(v, key)) return rc;
+  if (int rc = plan_hit_merge(v)) return rc;
   if (int rc = restore_info(v, 0)) return rc;
   HIPCHK(event(3, &e_ready));  // inputs staged and the counters cleared
   HIPCHK(hipEventRecord(e_ready, S.stream));
@@ -2300,7 +2387,12 @@ static int analyze_call(VarCall &v, cwbl_stats *stats) {
   // The searches run on S.sstream into two list buffers, the solves on S.stream: batch b + 1's
   // search (latency-bound, integer / fp32) overlaps batch b's solve (FP64-bound).  Search b
   // waits for the inputs and for the solve of b - 2 (same buffer); solve b waits for search b.
+  // A hit under CWBL_OPT_HIT_MERGE solves the cached batches of an info window in one launch
+  // (solve_hits_merged): restore_info, b2, the launch, dn, which every batch it covers has as
+  // its done event.
   const long long nbat = (long long)v.plan.size();
+  long long searched = -1;         // the batch that a merged launch's iteration searched ahead
+  hipEvent_t searched_ev = nullptr;  // the end of the search the solve waits for
   for (long long bi = 0; bi < nbat; ++bi) {
     const long long g0 = v.plan[bi].first;
     const int nb = v.plan[bi].second;
@@ -2326,9 +2418,32 @@ static int analyze_call(VarCall &v, cwbl_stats *stats) {
         crec ? C.off[bi] / AsmRecord<kTq4KP>::WORDS * FactorAux<kTq4KP>::WORDS : 0;
     double *const caux = crec && S.factor_reuse ? C.aux.as<double>() + aoff : nullptr;
     const bool hit = crec && v.reuse == 2;
+    if (hit && v.merge) {
+      // the cached batches of this window: [bi, be)
+      long long be = bi + 1;
+      while (be < v.ncached && v.plan[be].first + v.plan[be].second - v.win0 <= v.info_cap) ++be;
+      // a partial hit: the first batch past the cached ones is searched while they are solved
+      if (be == v.ncached && be < nbat) {
+        int *const nc = (be & 1) ? S.nbr_cnt2.as<int>() : S.nbr_cnt.as<int>();
+        int *const ni = (be & 1) ? S.nbr_idx2.as<int>() : S.nbr_idx.as<int>();
+        if (int rc = search_batch(v, be, nc, ni, a, b)) return rc;
+        v.search_ev.push_back({ev, ev + 1});
+        searched = be;
+        searched_ev = b;
+      }
+      if (int rc = solve_hits_merged(v, bi, be, b2, dn)) return rc;
+      v.solve_ev.push_back({ev + 2, ev + 3});
+      for (long long bj = bi; bj < be; ++bj) v.done_ev.push_back(ev + 3);
+      v.ev += 4;
+      bi = be - 1;
+      continue;
+    }
     if (!hit) {
-      if (int rc = search_batch(v, bi, ncnt, nidx, a, b)) return rc;
-      HIPCHK(hipStreamWaitEvent(S.stream, b, 0));
+      if (bi != searched) {
+        if (int rc = search_batch(v, bi, ncnt, nidx, a, b)) return rc;
+        searched_ev = b;
+      }
+      HIPCHK(hipStreamWaitEvent(S.stream, searched_ev, 0));
     }
     if (v.piped)
       if (int rc = upload_batch_var(v, bi)) return rc;
@@ -2348,7 +2463,7 @@ static int analyze_call(VarCall &v, cwbl_stats *stats) {
       if (v.piped_back && bi >= State::kSlots - 1)
         if (int rc = bounce_drain(v, bi - (State::kSlots - 1))) return rc;
     }
-    if (!hit) v.search_ev.push_back({ev, ev + 1});
+    if (!hit && bi != searched) v.search_ev.push_back({ev, ev + 1});
     v.solve_ev.push_back({ev + 2, ev + 3});
     v.done_ev.push_back(ev + 3);
     v.ev += 4;

@@ -301,6 +301,24 @@ hipError_t launch_solve_tq40_factor(hipStream_t s, int kp, SolveConsts c, SlabDe
                                     long long g0, int npts, const double *ws, const double *aux,
                                     int2 *info);
 
+// One launch for the hits of several cached batches (CWBL_OPT_HIT_MERGE): what
+// launch_solve_tq40_factor does once per segment, a segment being what one of its launches
+// covers (a cached batch, or a sub-batch of one).  Segment y is row y of a two-dimensional
+// grid, so that no wave holds points of two segments and the waves of a segment group its
+// points as its own launch would; the row is as wide as the largest segment, and the blocks
+// past a shorter one's last wave leave at once.
+struct HitSeg {
+  long long g0;   // first point
+  long long ord;  // ordinal of its first record and FactorAux entry in `ws` and `aux`; its
+                  // spare ones are at ord + ns
+  int ns;         // points (<= 2^19)
+  int info;       // its info from info[info]
+};
+// seg: the nseg <= 65535 segments, on the device; maxns: the largest one's points.
+hipError_t launch_solve_tq40_factor_merged(hipStream_t s, int kp, SolveConsts c, SlabDev slab,
+                                           const HitSeg *seg, int nseg, int maxns,
+                                           const double *ws, const double *aux, int2 *info);
+
 // cwbl_analyze_vars: the variables of a group share the record (A, b1) and so the factor
 // A = Q T Q^T; solve_tq40_multi_kernel (cwbl_tq40_multi.hip) tridiagonalises once per point
 // and replays the reflectors on every variable's x'.  The per-variable table goes to the

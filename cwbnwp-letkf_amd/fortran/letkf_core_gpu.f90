@@ -80,6 +80,9 @@ module letkf_core_gpu
     ! cwbl_set_option: the record cache keeps each point's factor A = Q T Q^T (1, default) or
     ! its assembled record (0)
     integer(c_int), parameter, public :: CWBL_OPT_FACTOR_REUSE = 17
+    ! cwbl_set_option: a call that hits the factor cache solves all its cached batches in one
+    ! launch per info window (1, default) or in one launch per batch (0)
+    integer(c_int), parameter, public :: CWBL_OPT_HIT_MERGE = 18
 
     type, bind(C), public :: cwbl_bin_grid         ! cwbl_bin_index
         real(c_float)  :: x0, y0, z0, binv

@@ -384,7 +384,7 @@ enum {
                                 * automatic, default: all levels of the column unless the
                                 * columns alone do not fill the device).  The result does not
                                 * depend on it; tests use it to force level splits */
-  CWBL_OPT_FACTOR_REUSE = 17   /* what CWBL_OPT_RECORD_REUSE keeps of a point: 1 (default) the
+  CWBL_OPT_FACTOR_REUSE = 17,  /* what CWBL_OPT_RECORD_REUSE keeps of a point: 1 (default) the
                                 * factor A = Q T Q^T of the record, written over its 6880 bytes
                                 * by the call that fills the cache, and 640 bytes more with the
                                 * reduction's step scalars, so a later call with an equal key
@@ -394,6 +394,12 @@ enum {
                                 * alone, so the cached batches, the key, the counters and
                                 * cwbl_reuse_info's batch counts do not depend on it; its
                                 * bytes_held includes the 640-byte part */
+  CWBL_OPT_HIT_MERGE = 18      /* a call that solves from the factor cache (a hit under
+                                * CWBL_OPT_FACTOR_REUSE: one variable, slab resident or staged
+                                * whole) issues 1 (default) one launch per info window for all
+                                * its cached batches, 0 one launch per cached batch.
+                                * Bit-identical results either way.  Nothing that is cached
+                                * depends on it: setting it leaves a filled cache valid */
 };
 int         cwbl_set_option(int option, long long value);
 
