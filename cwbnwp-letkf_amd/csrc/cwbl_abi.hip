@@ -226,7 +226,8 @@ enum KernelId {
   KT_SOLVE_TQ40_MULTI, KT_SOLVE_TQ40_COLUMN, KT_FILL_TQ40_FACTOR, KT_SOLVE_TQ40_FACTOR, KT_SOLVE_TQ_MULTI2, KT_SOLVE_TQ_MULTI4, KT_SOLVE_TQ_MULTI8,
   KT_BIG_HANDOFF, KT_TQB_TAIL, KT_BIG_HANDOFF_MULTI2, KT_BIG_HANDOFF_MULTI4,
   KT_BIG_HANDOFF_MULTI8, KT_TQB_TAIL_MULTI2, KT_TQB_TAIL_MULTI4, KT_TQB_TAIL_MULTI8,
-  KT_SOLVE_TQ, KT_SOLVE_TQ_BIG, KT_SOLVE_JACOBI, KT_TUNE_Q,
+  KT_SOLVE_TQ, KT_FILL_TQ_WAVE, KT_SOLVE_TQ_WAVE_FACTOR, KT_SOLVE_TQ_BIG, KT_SOLVE_JACOBI,
+  KT_TUNE_Q,
   KT_COUNT
 };
 struct KTime { long long launches = 0, points = 0; double ms = 0.0; };
@@ -243,8 +244,14 @@ struct KTime { long long launches = 0, points = 0; double ms = 0.0; };
 // tau go to an entry of their own per cached record (FactorAux), outside the budget, which
 // bounds the records alone: what is cached does not depend on the form.  A cache holds one
 // form only: the option bumps the generation, which is part of the key.
+// Wave reuse (CWBL_OPT_WAVE_REUSE): the same cache on the one-wavefront path at KP = 48, 56, 64.
+// A fill's solve, fill_tq_wave_kernel, assembles and tridiagonalises as solve_tq_kernel does and
+// leaves each cached point's WaveFactor<KP> in the batch's region; a hit runs
+// solve_tq_wave_factor_kernel on those and nothing before it.  One record is one factor (`words`),
+// steps' scalars included: the budget bounds all of it, and there is no FactorAux.
 struct RecordKey {
   unsigned long long gen;  // State::gen: obs set, cwbl_init constants, options
+  int kp;                  // the path's KP (the record path: kTq4KP)
   float multi_infl;        // inflat is on the record's diagonal
   int dims[7];             // nx, ny, nz, alt_nx, alt_ny, ix_lim, iy_lim
   cwbl_type_params gts[CWBL_NUM_GTS_TYPES], radar[CWBL_NUM_RADAR_TYPES];
@@ -261,6 +268,8 @@ struct RecordCache {
   // ordinal: batch b's entries start at entry off[b] / WORDS, sub-batch s0's s0 entries on.
   DevBuf rec, aux, info, sx, sy, salt, flag;
   PinBuf hflag;
+  size_t words = AsmRecord<kTq4KP>::WORDS;  // fp64 words of a record: AsmRecord or WaveFactor
+  bool wave = false;                         // the allocation last served the one-wavefront path
   std::vector<std::pair<long long, int>> plan;
   std::vector<size_t> off;
   long long pts = 0;
@@ -271,6 +280,7 @@ struct RecordCache {
   size_t bytes() const { return rec.n + aux.n + info.n + sx.n + sy.n + salt.n + flag.n; }
   void release() {
     valid = false;
+    wave = false;
     for (DevBuf *b : {&rec, &aux, &info, &sx, &sy, &salt, &flag}) b->release();
     hflag.release();
     plan.clear();
@@ -341,6 +351,7 @@ struct State {
   size_t reuse_budget = 0;        // CWBL_OPT_RECORD_REUSE in bytes (0: no reuse)
   bool factor_reuse = true;       // CWBL_OPT_FACTOR_REUSE: the cache keeps factors, not records
   bool hit_merge = true;          // CWBL_OPT_HIT_MERGE: one hit launch per info window
+  bool wave_reuse = false;        // CWBL_OPT_WAVE_REUSE: the factor cache of k = 41..64
   // the segment tables of a call's merged hit launches (HitSeg): written by the host, one
   // asynchronous copy per launch
   DevBuf hitseg;
@@ -501,6 +512,8 @@ std::string kernel_name(int id) {
     case KT_SOLVE_TQ40_COLUMN: return "solve_tq40_column_kernel<" + kp + ">";
     case KT_FILL_TQ40_FACTOR: return "fill_tq40_factor_kernel<" + kp + ">";
     case KT_SOLVE_TQ40_FACTOR: return "solve_tq40_factor_kernel<" + kp + ">";
+    case KT_FILL_TQ_WAVE: return "fill_tq_wave_kernel<" + kp + ">";
+    case KT_SOLVE_TQ_WAVE_FACTOR: return "solve_tq_wave_factor_kernel<" + kp + ">";
     case KT_BIG_HANDOFF:
       return S.kp == 128 ? "solve_tq_rows_kernel<128, 64>"
                          : "solve_tq_big_kernel<" + kp + ", false, " +
@@ -1085,10 +1098,14 @@ bool wave_path() { return !record_path() && S.kp <= kMaxWaveKP && !S.jacobi; }
 bool handoff_path() {
   return (S.kp == 96 || S.kp == kBigSplitKP) && S.big_split && S.k > big_split_j0(S.kp) + 2;
 }
+// the one-wavefront path's calls that fill and read the factor cache (CWBL_OPT_WAVE_REUSE;
+// accepted and ignored at the smaller KP)
+bool wave_reuse_path() { return S.wave_reuse && wave_path() && S.kp > kTq4KP; }
 
 void make_record_key(RecordKey &key, const cwbl_var_params *vp, const cwbl_slab *sl) {
   std::memset(&key, 0, sizeof key);
   key.gen = S.gen;
+  key.kp = S.kp;
   key.multi_infl = vp->multi_infl;
   const int dims[7] = {sl->nx, sl->ny, sl->nz, sl->alt_nx, sl->alt_ny, sl->ix_lim, sl->iy_lim};
   std::memcpy(key.dims, dims, sizeof dims);
@@ -1126,9 +1143,12 @@ int begin_fill(VarCall &v, const RecordKey &key) {
   C.plan = v.plan;
   C.off.clear();
   C.pts = 0;
+  C.wave = wave_reuse_path();
+  C.words = C.wave ? wave_factor_words(S.kp) : (size_t)AsmRecord<kTq4KP>::WORDS;
   size_t words = 0;
   for (const auto &b : v.plan) {
-    const size_t need = ((size_t)b.second + 1) * AsmRecord<kTq4KP>::WORDS;
+    // (+1: the spare record; the wave kernels read none, the region's layout is one)
+    const size_t need = ((size_t)b.second + 1) * C.words;
     if ((words + need) * sizeof(double) > S.reuse_budget) break;
     C.off.push_back(words);
     words += need;
@@ -1146,7 +1166,7 @@ int begin_fill(VarCall &v, const RecordKey &key) {
             C.rec.ensure(std::min(S.reuse_budget, need + need / 16)) == hipSuccess;
   // The steps' scalars of the factors, an entry per record: beside the budget's cut, like info
   // and the snapshot, with the same headroom; a cache of records holds none
-  if (S.factor_reuse) {
+  if (S.factor_reuse && !C.wave) {
     const size_t aneed =
         words / AsmRecord<kTq4KP>::WORDS * FactorAux<kTq4KP>::WORDS * sizeof(double);
     ok = ok && (aneed <= C.aux.n || C.aux.ensure(aneed + aneed / 16) == hipSuccess);
@@ -1546,7 +1566,9 @@ long long sub_batch(int nb, long long cap) {
 // b2 / dn: the events around the batch's solve (the record path times its kernel pair
 // between them).  crec (record path): the batch's region of the record cache, which a fill
 // assembles into and a hit (no lists, no assembly) solves from; null: S.wsa.  caux: that
-// region's FactorAux entries (a cached batch under factor reuse; else null and unused).
+// region's FactorAux entries (a cached batch under factor reuse; else null and unused).  On the
+// one-wavefront path crec is the batch's region of WaveFactors (CWBL_OPT_WAVE_REUSE): a fill
+// runs fill_tq_wave_kernel in solve_tq_kernel's place, a hit solve_tq_wave_factor_kernel.
 int solve_batch_path(VarCall &v, long long g0, int nb, const int *ncnt, const int *nidx,
                      int2 *infob, hipEvent_t b2, hipEvent_t dn, double *crec = nullptr,
                      bool hit = false, double *caux = nullptr) {
@@ -1662,6 +1684,13 @@ int solve_batch_path(VarCall &v, long long g0, int nb, const int *ncnt, const in
     HIPCHK(kt_end(S.stream, kt, nv == 2 ? KT_SOLVE_TQ_MULTI2 : nv == 4 ? KT_SOLVE_TQ_MULTI4
                                                                       : KT_SOLVE_TQ_MULTI8,
                   (long long)nb * v.lev));
+  } else if (crec) {  // a cached batch of the factor cache (CWBL_OPT_WAVE_REUSE)
+    if (hit) {
+      HIPCHK(launch_solve_tq_wave_factor(S.stream, S.kp, c, sd, g0, nb, crec, infob));
+    } else {
+      HIPCHK(launch_fill_tq_wave(S.stream, S.kp, dtrees, c, sd, g0, nb, ncnt, nidx, infob, crec));
+    }
+    HIPCHK(kt_end(S.stream, kt, hit ? KT_SOLVE_TQ_WAVE_FACTOR : KT_FILL_TQ_WAVE, nb));
   } else {
     HIPCHK(launch_solve_tq(S.stream, S.kp, false, dtrees, c, sd, g0, nb, ncnt, nidx, nullptr,
                            nullptr, nullptr, nullptr, nullptr, infob));
@@ -1949,6 +1978,7 @@ int cwbl_init(const cwbl_init_params *p) {
   S.column_levels = 0;
   S.factor_reuse = true;
   S.hit_merge = true;
+  S.wave_reuse = false;
   S.ncu = prop.multiProcessorCount;
   std::memset(&P, 0, sizeof P);
   std::memset(&CI, 0, sizeof CI);
@@ -2048,6 +2078,11 @@ int cwbl_set_option(int option, long long value) {
     case CWBL_OPT_FACTOR_REUSE:
       if (!range(0, 1)) break;
       S.factor_reuse = value == 1;  // (the new generation voids a cache of the other form)
+      return CWBL_OK;
+    case CWBL_OPT_WAVE_REUSE:
+      if (!range(0, 1)) break;
+      S.wave_reuse = value == 1;
+      if (S.cache.wave) S.cache.release();  // off holds no memory (a record cache keeps its own)
       return CWBL_OK;
     default:
       return fail(CWBL_ERR_ARG, "cwbl_set_option: unknown option %d", option);
@@ -2220,8 +2255,9 @@ static long long hit_segments(int nb, long long *Bs_out = nullptr) {
 
 // Whether the call's cached batches go out merged, and room for their segment tables.
 static int plan_hit_merge(VarCall &v) {
-  v.merge = S.hit_merge && v.reuse == 2 && S.factor_reuse && !v.group && !v.colshare &&
-            !v.piped && !v.piped_back && !v.bounce && v.ncached > 0;
+  // (the record path's: a hit of the one-wavefront path's cache is one launch per batch)
+  v.merge = S.hit_merge && record_path() && v.reuse == 2 && S.factor_reuse && !v.group &&
+            !v.colshare && !v.piped && !v.piped_back && !v.bounce && v.ncached > 0;
   if (!v.merge) return CWBL_OK;
   long long nseg = 0;
   for (long long bi = 0; bi < v.ncached; ++bi) nseg += hit_segments(v.plan[bi].second);
@@ -2313,7 +2349,8 @@ static int analyze_call(VarCall &v, cwbl_stats *stats) {
   CI.reason = column_reason(v);
   const bool col_candidate = CI.reason == CWBL_COLUMN_SHARED;
   const bool reuse_on =
-      !v.group && !col_candidate && record_path() && S.reuse_budget > 0 && npts > 0;
+      !v.group && !col_candidate && (record_path() || wave_reuse_path()) &&
+      S.reuse_budget > 0 && npts > 0;
   RecordKey key;
   bool staged = false;
   if (reuse_on) {
@@ -2414,9 +2451,9 @@ static int analyze_call(VarCall &v, cwbl_stats *stats) {
     HIPCHK(event(ev + 3, &dn));
     // a cached batch: its region of the record cache; on a hit neither lists nor assembly
     double *const crec = bi < v.ncached ? C.rec.as<double>() + C.off[bi] : nullptr;
-    const size_t aoff =
-        crec ? C.off[bi] / AsmRecord<kTq4KP>::WORDS * FactorAux<kTq4KP>::WORDS : 0;
-    double *const caux = crec && S.factor_reuse ? C.aux.as<double>() + aoff : nullptr;
+    const size_t aoff = crec ? C.off[bi] / C.words * FactorAux<kTq4KP>::WORDS : 0;
+    double *const caux =
+        crec && S.factor_reuse && !C.wave ? C.aux.as<double>() + aoff : nullptr;
     const bool hit = crec && v.reuse == 2;
     if (hit && v.merge) {
       // the cached batches of this window: [bi, be)

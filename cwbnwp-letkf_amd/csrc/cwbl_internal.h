@@ -420,6 +420,39 @@ hipError_t launch_solve_tqb_tail_multi(hipStream_t s, int kp, SolveConsts c, Sla
                                        const Tq40Vars &vars, long long g0, int npts, double *ws,
                                        int2 *info);
 
+// The factor cache of the one-wavefront path at KP = 48, 56, 64 (CWBL_OPT_WAVE_REUSE,
+// cwbl_tq_wave.hip).  What it keeps of a point, in fp64 words: T's diagonal and off-diagonal
+// as sm.tq[i][0] and sm.tq[i][1] hold them after solve_tq_kernel's loop, Q^T b1, and per step j
+// tau_j, the factor scal_j that dlarfg scales x by (both the bits the fill's dlarfg returned) and
+// the unscaled, masked pivot column x: rows j + 1 .. KP-1 (row j + 1 is 0) as consecutive words,
+// one per lane.  A hit forms v = x scal where the single kernel forms it.
+template <int KP>
+struct WaveFactor {
+  static constexpr int D = 0;           // d_i (KP)
+  static constexpr int C = KP;          // c(i-1, i): 0 at i = 0 (KP)
+  static constexpr int U1 = 2 * KP;     // Q^T b1 (KP)
+  static constexpr int TAU = 3 * KP;    // tau_j, 0 for a step that ran no reflector (KP)
+  static constexpr int SCAL = 4 * KP;   // scal_j (KP; unwritten where step j left early)
+  static constexpr int COL = 5 * KP;    // the columns
+  // row j + 1 of column j; row i >= j + 1 at col(j) + i - (j + 1)
+  __host__ __device__ static constexpr int col(int j) {
+    return COL + j * (KP - 1) - j * (j - 1) / 2;
+  }
+  static constexpr int WORDS = KP * (KP - 1) / 2 + 5 * KP;
+};
+static_assert(WaveFactor<64>::col(63) == WaveFactor<64>::WORDS, "the columns fill the factor");
+constexpr size_t wave_factor_words(int kp) {
+  return kp == 48 ? WaveFactor<48>::WORDS : kp == 56 ? WaveFactor<56>::WORDS
+                                                      : WaveFactor<64>::WORDS;
+}
+// fill: launch_solve_tq's slab mode, which also leaves the npts factors at `fac`; the hit: the
+// same analysis from them and from info[i].x = p of the fill (no lists, no trees).
+hipError_t launch_fill_tq_wave(hipStream_t s, int kp, const TreeDesc *trees, SolveConsts c,
+                               SlabDev slab, long long g0, int npts, const int *nbr_cnt,
+                               const int *nbr_idx, int2 *info, double *fac);
+hipError_t launch_solve_tq_wave_factor(hipStream_t s, int kp, SolveConsts c, SlabDev slab,
+                                       long long g0, int npts, const double *fac, int2 *info);
+
 // KP = 96, 128: one 256-thread workgroup per point (cwbl_tq_big.hip)
 hipError_t launch_solve_tq_big(hipStream_t s, int kp, bool assembled, const TreeDesc *trees,
                                SolveConsts c, SlabDev slab, long long g0, int npts,

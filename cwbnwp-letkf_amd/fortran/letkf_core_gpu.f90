@@ -83,6 +83,9 @@ module letkf_core_gpu
     ! cwbl_set_option: a call that hits the factor cache solves all its cached batches in one
     ! launch per info window (1, default) or in one launch per batch (0)
     integer(c_int), parameter, public :: CWBL_OPT_HIT_MERGE = 18
+    ! cwbl_set_option: calls of one variable at k = 41..64 keep each point's factor for the next
+    ! call with the same localisation (1; 0, default: off), within CWBL_OPT_RECORD_REUSE's budget
+    integer(c_int), parameter, public :: CWBL_OPT_WAVE_REUSE = 19
 
     type, bind(C), public :: cwbl_bin_grid         ! cwbl_bin_index
         real(c_float)  :: x0, y0, z0, binv

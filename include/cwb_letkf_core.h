@@ -394,12 +394,26 @@ enum {
                                 * alone, so the cached batches, the key, the counters and
                                 * cwbl_reuse_info's batch counts do not depend on it; its
                                 * bytes_held includes the 640-byte part */
-  CWBL_OPT_HIT_MERGE = 18      /* a call that solves from the factor cache (a hit under
+  CWBL_OPT_HIT_MERGE = 18,     /* a call that solves from the factor cache (a hit under
                                 * CWBL_OPT_FACTOR_REUSE: one variable, slab resident or staged
                                 * whole) issues 1 (default) one launch per info window for all
                                 * its cached batches, 0 one launch per cached batch.
                                 * Bit-identical results either way.  Nothing that is cached
                                 * depends on it: setting it leaves a filled cache valid */
+  CWBL_OPT_WAVE_REUSE = 19     /* 1: cwbl_analyze_var on the one-wavefront path at k = 41..64
+                                * (default solver) keeps each point's factor A = Q T Q^T for the
+                                * next call, within the CWBL_OPT_RECORD_REUSE budget (0 there
+                                * turns this cache off too): KP (KP - 1) / 2 + 5 KP fp64 words per
+                                * point at KP = 48, 56, 64 (10.9, 14.6, 18.7 KB).  A later call
+                                * with an equal key (the record cache's, and KP) and bit-equal
+                                * coordinates runs no obs preparation, search, assembly or
+                                * tridiagonalisation: one solve_tq_wave_factor_kernel per cached
+                                * batch.  Bit-identical results and equal counters; reported
+                                * through cwbl_reuse_info like the record cache.  0 (default):
+                                * nothing is kept and the path runs as without the option.
+                                * Accepted and ignored at k <= 16 and at k = 17..40 under
+                                * CWBL_OPT_SPLIT40 = 0.  Group calls and column-shared calls
+                                * neither read, fill nor invalidate the cache */
 };
 int         cwbl_set_option(int option, long long value);
 
