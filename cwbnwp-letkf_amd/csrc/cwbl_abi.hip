@@ -352,6 +352,8 @@ struct State {
   bool factor_reuse = true;       // CWBL_OPT_FACTOR_REUSE: the cache keeps factors, not records
   bool hit_merge = true;          // CWBL_OPT_HIT_MERGE: one hit launch per info window
   bool wave_reuse = false;        // CWBL_OPT_WAVE_REUSE: the factor cache of k = 41..64
+  bool host_pipe = false;         // CWBL_OPT_HOST_PIPE: group, column-shared and tune_q calls
+                                  // pipe their host slabs per batch
   // the segment tables of a call's merged hit launches (HitSeg): written by the host, one
   // asynchronous copy per launch
   DevBuf hitseg;
@@ -623,6 +625,7 @@ int bin_div_for(const HostTree &t, int dim) {
 
 cwbl_reuse_info_t R;  // cwbl_reuse_info: what the current cwbl_analyze_var reused
 cwbl_column_info_t CI;  // cwbl_column_info: what it shared per column (CWBL_OPT_COLUMN_SHARE)
+cwbl_transfer_info_t TI;  // cwbl_transfer_info: how it moved a host slab's var
 
 // ---- cwbl_prep_info: what the current cwbl_analyze_var spends on its search index -----------
 cwbl_prep_info_t P;
@@ -1053,8 +1056,13 @@ struct VarCall {
   // host-memory slab: x, y, alt staged first; var piped batch by batch (piped: the analysed
   // region is the whole horizontal slab, so a batch's points are contiguous in every member
   // plane) or moved whole; a pageable var page-locked in place (registered) or, failing that,
-  // through the library's page-locked bounce slots
+  // through the library's page-locked bounce slots.  A group's and a column-shared call's var
+  // move whole unless CWBL_OPT_HOST_PIPE pipes them (never through the slots).  reg: the
+  // arrays page-locked for the call; tune_batch: tune_q runs per batch, behind its solve, so
+  // that a call with tune_q pipes its analysis back as well (CWBL_OPT_HOST_PIPE)
   bool host = false, piped = false, piped_back = false, bounce = false, registered = false;
+  bool tune_batch = false;
+  std::vector<float *> reg;
   std::vector<TreeDesc> descs;
   // index mode 1: the cache entry of every descriptor, and whether the tree searches' table
   // (S.tdesc_tree: the trees that exist, with their own rdata) has been uploaded
@@ -1065,7 +1073,8 @@ struct VarCall {
   long long B = 0, Bc = 0, info_cap = 0, win0 = 0;
   SolveConsts c{};
   float rbox = 0.0f;
-  // timing events S.events[ev..] (four per batch: search begin/end, solve begin/end) and
+  // timing events S.events[ev..] (four per batch: search begin/end, solve begin/end; under
+  // tune_batch a fifth, the end of the batch's tune_q) and
   // ordering events S.cevents[cev..] of the piped copies
   int ev = 4, cev = 0;
   std::vector<std::pair<int, int>> search_ev, solve_ev;
@@ -1260,11 +1269,18 @@ int stage_slab(VarCall &v) {
   const size_t balt = (size_t)sl->alt_nx * sl->alt_ny * sl->nz * 4;
   v.bvar = (size_t)v.L * S.k * 4;
   v.host = sl->memory != CWBL_MEM_DEVICE;
-  // (a group's host slabs move whole, from wherever they lie: not piped, page-locked or bounced)
-  // (so do a column-shared call's: its batches are columns, not contiguous runs of var)
+  // A group's host slabs move whole, from wherever they lie: not piped, page-locked or bounced.
+  // So do a column-shared call's (its batches are columns, not contiguous runs of var).  Under
+  // CWBL_OPT_HOST_PIPE both are piped like a single call's, when every var is page-locked or
+  // can be for the call; they have no bounce-slot mode.
   const bool whole = v.group || v.colshare;
-  v.piped = !whole && v.host && sl->ix_lim == sl->nx && sl->iy_lim == sl->ny;
-  v.piped_back = v.piped && !v.vp->tune_q;  // tune_q touches the whole slab afterwards
+  const bool region = sl->ix_lim == sl->nx && sl->iy_lim == sl->ny;
+  bool tune = false;
+  for (int i = 0; i < v.nvar; ++i) tune = tune || v.vp[i].tune_q != 0;
+  int reason = CWBL_TRANSFER_PIPED;
+  if (!region) reason = CWBL_TRANSFER_REASON_REGION;
+  else if (!S.host_pipe && (whole || tune)) reason = CWBL_TRANSFER_REASON_OFF;
+  v.piped = v.host && region && (!whole || S.host_pipe);
   // pageable var (a Fortran host's ordinary arrays): copies from pageable memory are staged by
   // the runtime and do not overlap.  It is page-locked in place for the call (r4, C2 from
   // pageable numpy arrays: 58.7 M pts/s, against 58.2 M page-locked and 50.8 M through the
@@ -1273,11 +1289,43 @@ int stage_slab(VarCall &v) {
   v.bounce = !whole && v.host && v.bvar > 0 && !host_pinned(sl->var);
   if (v.bounce && S.pageable_register) {
     if (hipHostRegister(sl->var, v.bvar, hipHostRegisterDefault) == hipSuccess) {
-      v.registered = true;
+      v.reg.push_back(sl->var);
       v.bounce = false;
     } else {
       (void)hipGetLastError();
     }
+  }
+  if (whole && v.piped && v.bvar > 0) {  // every var page-locked, or the call moves whole
+    for (int i = 0; i < v.nvar && v.piped; ++i) {
+      if (host_pinned(v.sl[i].var)) continue;
+      if (!S.pageable_register) {
+        reason = CWBL_TRANSFER_REASON_BOUNCE;
+        v.piped = false;
+      } else if (hipHostRegister(v.sl[i].var, v.bvar, hipHostRegisterDefault) == hipSuccess) {
+        v.reg.push_back(v.sl[i].var);
+      } else {
+        (void)hipGetLastError();
+        reason = CWBL_TRANSFER_REASON_REGISTER;
+        v.piped = false;
+      }
+    }
+    if (!v.piped) {  // undo the registrations made: whole moves take var from where it lies
+      for (float *p : v.reg) (void)hipHostUnregister(p);
+      v.reg.clear();
+    }
+  }
+  v.registered = !v.reg.empty();
+  // tune_q after the last batch touches the whole slab, so the analysis then goes back whole;
+  // per batch (CWBL_OPT_HOST_PIPE) it leaves every batch final behind its own solve
+  v.piped_back = v.piped && (!tune || S.host_pipe);
+  v.tune_batch = v.piped_back && tune;
+  TI.host = v.host;
+  if (v.host) {
+    TI.piped = v.piped;
+    TI.piped_back = v.piped_back;
+    TI.registered = (int)v.reg.size();
+    TI.bounce = v.bounce;
+    TI.reason = reason;
   }
   if (!v.host) {
     sd.x = sl->x; sd.y = sl->y; sd.alt = sl->alt;
@@ -1292,8 +1340,10 @@ int stage_slab(VarCall &v) {
     HIPCHK(S.svar.ensure(v.bvar * (size_t)v.nvar));
     for (int i = 0; i < v.nvar; ++i) {
       v.tv.var[i] = S.svar.as<float>() + (size_t)i * (size_t)v.L * S.k;
-      if (v.bvar > 0 && !v.piped && !v.bounce)
+      if (v.bvar > 0 && !v.piped && !v.bounce) {
         HIPCHK(hipMemcpyAsync(v.tv.var[i], v.sl[i].var, v.bvar, hipMemcpyHostToDevice, S.stream));
+        TI.bytes_whole_up += (long long)v.bvar;
+      }
     }
   }
   sd.var = v.tv.var[0];
@@ -1345,6 +1395,7 @@ int bounce_whole(VarCall &v, bool up) {
   int pcn = 0;
   const size_t pitch = (size_t)v.L * 4;
   float *const hvar = v.sl->var;
+  (up ? TI.bytes_whole_up : TI.bytes_whole_down) += (long long)v.bvar;
   for (long long c0 = 0, i = 0; c0 < v.L; c0 += v.Bc, ++i) {
     const int cn = (int)std::min<long long>(v.Bc, v.L - c0);
     PinBuf &slot = up ? S.pin_in[i & 1] : S.pin_out[i & 1];
@@ -1498,49 +1549,85 @@ int search_batch(VarCall &v, long long bi, int *ncnt, int *nidx, hipEvent_t a, h
                                               : fail(CWBL_ERR_HIP, "search event record failed");
 }
 
-// A host slab's var columns of batch bi up (k rows of nb floats, member pitch L) on S.h2d,
-// from the caller's page-locked array or from the batch's bounce slot; S.stream waits.
+// The rows of batch bi in a host slab's var and in its staged copy: k rows of nb floats at the
+// member pitch L per variable, variable i at its part of S.svar; for a column-shared call, whose
+// batch is the columns [g0, g0 + nb), nz k rows at the plane pitch nx ny (a column run is
+// contiguous in every (level, member) plane).  One 2-D copy per variable either way.
+struct BatchRows {
+  size_t pitch, rows, width;
+};
+BatchRows batch_rows(const VarCall &v, int nb) {
+  if (v.colshare)
+    return {(size_t)v.sl->nx * v.sl->ny * 4, (size_t)v.sl->nz * S.k, (size_t)nb * 4};
+  return {(size_t)v.L * 4, (size_t)S.k, (size_t)nb * 4};
+}
+
+// A host slab's var columns of batch bi up on S.h2d, from the caller's page-locked arrays (a
+// group: every variable's, then one event) or from the batch's bounce slot; S.stream waits.
 int upload_batch_var(VarCall &v, long long bi) {
   const long long g0 = v.plan[bi].first;
   const int nb = v.plan[bi].second;
   hipEvent_t hv;
   const int hv_i = v.cev++;
   HIPCHK(cevent(hv_i, &hv));
-  const size_t pitch = (size_t)v.L * 4;
+  const BatchRows r = batch_rows(v, nb);
   if (v.bounce) {  // slot bi % kSlots, filled before this batch (bounce_fill)
     if (bi == 0)
       if (int rc = bounce_fill(v, 0)) return rc;
-    HIPCHK(hipMemcpy2DAsync(S.svar.as<float>() + g0, pitch, S.pin_in[bi % State::kSlots].p,
-                            (size_t)nb * 4, (size_t)nb * 4, (size_t)S.k, hipMemcpyHostToDevice,
-                            S.h2d));
+    HIPCHK(hipMemcpy2DAsync(S.svar.as<float>() + g0, r.pitch, S.pin_in[bi % State::kSlots].p,
+                            r.width, r.width, r.rows, hipMemcpyHostToDevice, S.h2d));
   } else {
-    HIPCHK(hipMemcpy2DAsync(S.svar.as<float>() + g0, pitch, v.sl->var + g0, pitch,
-                            (size_t)nb * 4, (size_t)S.k, hipMemcpyHostToDevice, S.h2d));
+    for (int i = 0; i < v.nvar; ++i)
+      HIPCHK(hipMemcpy2DAsync(S.svar.as<float>() + (size_t)i * (size_t)v.L * S.k + g0, r.pitch,
+                              v.sl[i].var + g0, r.pitch, r.width, r.rows, hipMemcpyHostToDevice,
+                              S.h2d));
   }
+  TI.bytes_piped_up += (long long)(r.width * r.rows) * v.nvar;
   HIPCHK(hipEventRecord(hv, S.h2d));
   v.h2d_done.push_back(hv_i);
   HIPCHK(hipStreamWaitEvent(S.stream, hv, 0));
   return CWBL_OK;
 }
 
-// Batch bi's analysis back to a host slab behind its solve (event dn) on S.d2h.
+// Batch bi's analysis back to a host slab on S.d2h behind the event dn: the one after its
+// solve, or after its tune_q (tune_batch_var).
 int return_batch_var(VarCall &v, long long bi, hipEvent_t dn) {
   const long long g0 = v.plan[bi].first;
   const int nb = v.plan[bi].second;
   HIPCHK(hipStreamWaitEvent(S.d2h, dn, 0));
-  const size_t pitch = (size_t)v.L * 4;
+  const BatchRows r = batch_rows(v, nb);
   if (v.bounce) {  // into slot bi % kSlots (drained kSlots - 1 batches later)
     hipEvent_t dv;
     const int dv_i = v.cev++;
     HIPCHK(cevent(dv_i, &dv));
-    HIPCHK(hipMemcpy2DAsync(S.pin_out[bi % State::kSlots].p, (size_t)nb * 4,
-                            S.svar.as<float>() + g0, pitch, (size_t)nb * 4, (size_t)S.k,
-                            hipMemcpyDeviceToHost, S.d2h));
+    HIPCHK(hipMemcpy2DAsync(S.pin_out[bi % State::kSlots].p, r.width, S.svar.as<float>() + g0,
+                            r.pitch, r.width, r.rows, hipMemcpyDeviceToHost, S.d2h));
     HIPCHK(hipEventRecord(dv, S.d2h));
     v.d2h_done.push_back(dv_i);
   } else {
-    HIPCHK(hipMemcpy2DAsync(v.sl->var + g0, pitch, S.svar.as<float>() + g0, pitch,
-                            (size_t)nb * 4, (size_t)S.k, hipMemcpyDeviceToHost, S.d2h));
+    for (int i = 0; i < v.nvar; ++i)
+      HIPCHK(hipMemcpy2DAsync(v.sl[i].var + g0, r.pitch,
+                              S.svar.as<float>() + (size_t)i * (size_t)v.L * S.k + g0, r.pitch,
+                              r.width, r.rows, hipMemcpyDeviceToHost, S.d2h));
+  }
+  TI.bytes_piped_down += (long long)(r.width * r.rows) * v.nvar;
+  return CWBL_OK;
+}
+
+// letkf_tune_q over batch (g0, nb) on S.stream, for the variables that ask for it: the batch's
+// points, or for a column-shared call its columns at every level.  The kernel is pointwise
+// (each point reads and writes only its own k members), and the batches of a piped call cover
+// every point of the slab, the ones the solve skips (p = 0) included.
+int tune_batch_var(VarCall &v, long long g0, int nb) {
+  for (int i = 0; i < v.nvar; ++i) {
+    if (!v.vp[i].tune_q) continue;
+    SlabDev sdi = v.colshare ? v.full : v.sd;  // (a shared call: the slab, not its column view)
+    sdi.var = S.svar.as<float>() + (size_t)i * (size_t)v.L * S.k;
+    int kt;
+    HIPCHK(kt_begin(S.stream, &kt));
+    HIPCHK(launch_tune_q_range(S.stream, sdi, S.k, g0, nb, v.nlev, v.colshare ? v.ncol : 0));
+    HIPCHK(kt_end(S.stream, kt, KT_TUNE_Q, (long long)nb * v.nlev));
+    ++TI.tune_q_launches;
   }
   return CWBL_OK;
 }
@@ -1832,7 +1919,8 @@ int finish_call(VarCall &v, cwbl_stats &st) {
     if (int rc = keep_info(v, v.npts)) return rc;
   }
   int ev = v.ev;
-  for (int i = 0; i < v.nvar; ++i) {  // letkf_tune_q on the variables that ask for it
+  // letkf_tune_q on the variables that ask for it (tune_batch: every batch has had its own)
+  for (int i = 0; i < v.nvar && !v.tune_batch; ++i) {
     if (!v.vp[i].tune_q) continue;
     hipEvent_t a, b;
     HIPCHK(event(ev, &a));
@@ -1844,6 +1932,7 @@ int finish_call(VarCall &v, cwbl_stats &st) {
     HIPCHK(kt_begin(S.stream, &kt));
     HIPCHK(launch_tune_q(S.stream, sdi, S.k));
     HIPCHK(kt_end(S.stream, kt, KT_TUNE_Q, v.npts * v.nlev));
+    ++TI.tune_q_launches;
     HIPCHK(hipEventRecord(b, S.stream));
     v.solve_ev.push_back({ev, ev + 1});
     ev += 2;
@@ -1852,8 +1941,10 @@ int finish_call(VarCall &v, cwbl_stats &st) {
   HIPCHK(event(ev, &e_end));
   HIPCHK(event(ev + 1, &e_back));
   if (v.host && !v.piped_back && !v.bounce)
-    for (int i = 0; i < v.nvar; ++i)
+    for (int i = 0; i < v.nvar; ++i) {
       HIPCHK(hipMemcpyAsync(v.sl[i].var, v.tv.var[i], v.bvar, hipMemcpyDeviceToHost, S.stream));
+      TI.bytes_whole_down += (long long)v.bvar;
+    }
   if (v.piped_back) {  // the call returns after the last batch's copy back
     HIPCHK(hipEventRecord(e_back, S.d2h));
     HIPCHK(hipStreamWaitEvent(S.stream, e_back, 0));
@@ -1979,9 +2070,11 @@ int cwbl_init(const cwbl_init_params *p) {
   S.factor_reuse = true;
   S.hit_merge = true;
   S.wave_reuse = false;
+  S.host_pipe = false;
   S.ncu = prop.multiProcessorCount;
   std::memset(&P, 0, sizeof P);
   std::memset(&CI, 0, sizeof CI);
+  std::memset(&TI, 0, sizeof TI);
   S.lead_div = 0;
   S.serial_search = false;
 #ifdef CWBL_DEBUG_KNOBS
@@ -1999,12 +2092,13 @@ int cwbl_init(const cwbl_init_params *p) {
 int cwbl_set_option(int option, long long value) {
   if (!S.inited) return fail(CWBL_ERR_STATE, "cwbl_set_option before cwbl_init");
   auto range = [&](long long lo, long long hi) { return value >= lo && value <= hi; };
-  if (option == CWBL_OPT_HIT_MERGE) {
-    // how the cached batches are launched, not what is cached: the generation stays
+  if (option == CWBL_OPT_HIT_MERGE || option == CWBL_OPT_HOST_PIPE) {
+    // how the cached batches are launched, or how a host slab travels, not what is cached: the
+    // generation stays
     if (!range(0, 1))
       return fail(CWBL_ERR_ARG, "cwbl_set_option: value %lld out of range for option %d", value,
                   option);
-    S.hit_merge = value == 1;
+    (option == CWBL_OPT_HIT_MERGE ? S.hit_merge : S.host_pipe) = value == 1;
     return CWBL_OK;
   }
   ++S.gen;  // options change the neighbour order and the batch plan: kept records are void
@@ -2139,6 +2233,13 @@ int cwbl_column_info(cwbl_column_info_t *out) {
   return CWBL_OK;
 }
 
+int cwbl_transfer_info(cwbl_transfer_info_t *out) {
+  if (int rc = require_device()) return rc;
+  if (!out) return fail(CWBL_ERR_ARG, "cwbl_transfer_info: null argument");
+  *out = TI;
+  return CWBL_OK;
+}
+
 int cwbl_finalize(void) {
   if (S.inited) {
     (void)hipStreamSynchronize(S.stream);
@@ -2236,6 +2337,7 @@ static int begin_call(const cwbl_slab *sl) {
   std::memset(&P, 0, sizeof P);
   std::memset(&R, 0, sizeof R);
   std::memset(&CI, 0, sizeof CI);
+  std::memset(&TI, 0, sizeof TI);
   g_pspans.clear();
   g_pev_used = 0;
   return CWBL_OK;
@@ -2327,15 +2429,16 @@ static int analyze_call(VarCall &v, cwbl_stats *stats) {
     if (stats) *stats = st;
     return CWBL_OK;
   };
-  struct Unregister {  // a page-locked-in-place var, on every return path, once no queued
+  struct Unregister {  // every page-locked-in-place var, on every return path, once no queued
     VarCall &v;        // copy can still touch it
     ~Unregister() {
-      if (!v.registered) return;
+      if (v.reg.empty()) return;
       (void)hipStreamSynchronize(S.h2d);
       (void)hipStreamSynchronize(S.d2h);
       (void)hipStreamSynchronize(S.stream);
       (void)hipGetLastError();
-      (void)hipHostUnregister(v.sl->var);
+      for (float *p : v.reg) (void)hipHostUnregister(p);
+      v.reg.clear();
     }
   } unreg{v};
 
@@ -2492,8 +2595,15 @@ static int analyze_call(VarCall &v, cwbl_stats *stats) {
       return rc;
     }
     HIPCHK(hipEventRecord(dn, S.stream));  // this batch's lists are free again
+    hipEvent_t back = dn;  // ... and its analysis final, unless tune_q follows
+    if (v.tune_batch) {    // timed from dn to an event of its own, which the copy back waits for
+      if (int rc = tune_batch_var(v, g0, nb)) return rc;
+      HIPCHK(event(ev + 4, &back));
+      HIPCHK(hipEventRecord(back, S.stream));
+      v.solve_ev.push_back({ev + 3, ev + 4});
+    }
     if (v.piped_back)
-      if (int rc = return_batch_var(v, bi, dn)) return rc;
+      if (int rc = return_batch_var(v, bi, back)) return rc;
     if (v.bounce && v.piped) {  // host side while the GPU works: next batch in, bi - 2 out
       if (bi + 1 < nbat)
         if (int rc = bounce_fill(v, bi + 1)) return rc;
@@ -2503,7 +2613,7 @@ static int analyze_call(VarCall &v, cwbl_stats *stats) {
     if (!hit && bi != searched) v.search_ev.push_back({ev, ev + 1});
     v.solve_ev.push_back({ev + 2, ev + 3});
     v.done_ev.push_back(ev + 3);
-    v.ev += 4;
+    v.ev += v.tune_batch ? 5 : 4;
   }
   if (int rc = finish_call(v, st)) return rc;
   if (v.reuse == 1) {  // the fill is complete: the next call may solve from it

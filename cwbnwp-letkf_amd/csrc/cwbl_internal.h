@@ -210,6 +210,11 @@ hipError_t launch_scale(hipStream_t s, float *x, long long n, float alpha);
 
 // letkf_tune_q over the analysed region of s.var (module_letkf_core.f90:702-733)
 hipError_t launch_tune_q(hipStream_t st, SlabDev s, int k);
+// ... over nrun runs of n points of that region, run r from point g0 + r * stride (a batch of
+// a piped host slab: one run; a column batch of a column-shared call: one run per level,
+// stride = ix_lim * iy_lim).  hipErrorInvalidValue when a run leaves the region.
+hipError_t launch_tune_q_range(hipStream_t st, SlabDev s, int k, long long g0, long long n,
+                               int nrun = 1, long long stride = 0);
 
 // depth: the deepest tree's level count (tree_depth), which sizes the traversal stacks.
 // obs_slots (CWBL_OPT_INDEX = 1): the columns are numbered by obs index, so the analysis lists

@@ -486,10 +486,13 @@ hipError_t launch_search_single(hipStream_t s, const TreeDesc *tree, int depth, 
 // `sum(var, mask=var>0)`, :720); a point with no positive member gets ratio = 0/0 (or x/0),
 // so its non-negative members become NaN (Q3, replicated).  HBM bound: 2 reads + 1 write of
 // the k values, coalesced across threads (neighbouring points are adjacent in memory).
+// The launch covers gridDim.y runs of n points: run r is the points g0 + r * stride + [0, n) of
+// the region (the whole region: one run from 0; launch_tune_q_range).
 __global__ void __launch_bounds__(256)
-tune_q_kernel(SlabDev s, int k, long long npts) {
-  const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (g >= npts) return;
+tune_q_kernel(SlabDev s, int k, long long g0, long long n, long long stride) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= n) return;
+  const long long g = g0 + (long long)blockIdx.y * stride + t;
   const int i = (int)(g % s.ix_lim);
   const long long r = g / s.ix_lim;
   const int j = (int)(r % s.iy_lim);
@@ -509,10 +512,19 @@ tune_q_kernel(SlabDev s, int k, long long npts) {
 }
 
 hipError_t launch_tune_q(hipStream_t st, SlabDev s, int k) {
+  return launch_tune_q_range(st, s, k, 0, (long long)s.ix_lim * s.iy_lim * s.nz);
+}
+
+hipError_t launch_tune_q_range(hipStream_t st, SlabDev s, int k, long long g0, long long n,
+                               int nrun, long long stride) {
   const long long npts = (long long)s.ix_lim * s.iy_lim * s.nz;
-  if (npts <= 0) return hipSuccess;
-  hipLaunchKernelGGL(tune_q_kernel, dim3((unsigned)((npts + 255) / 256)), dim3(256), 0, st, s,
-                     k, npts);
+  if (n <= 0 || nrun <= 0) return hipSuccess;
+  if (g0 < 0 || stride < 0 || g0 + (nrun - 1) * stride + n > npts) return hipErrorInvalidValue;
+  for (int r0 = 0; r0 < nrun; r0 += 65535) {  // gridDim.y
+    const int nr = std::min(65535, nrun - r0);
+    hipLaunchKernelGGL(tune_q_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)nr), dim3(256),
+                       0, st, s, k, g0 + r0 * stride, n, stride);
+  }
   return hipGetLastError();
 }
 

@@ -30,7 +30,7 @@ OPT_SOLVER, OPT_SPLIT40, OPT_SPLIT40_BATCH, OPT_SEARCH = 1, 2, 3, 5
 OPT_BIG_PATH, OPT_BIG_BATCH, OPT_PAGEABLE, OPT_BIN_DIV, OPT_LEAD_DIV, OPT_MAX_BATCH = 6, 7, 8, 9, 10, 11
 OPT_INFO_WINDOW, OPT_INDEX, OPT_RECORD_REUSE = 12, 13, 14
 OPT_COLUMN_SHARE, OPT_COLUMN_LEVELS, OPT_FACTOR_REUSE, OPT_HIT_MERGE = 15, 16, 17, 18
-OPT_WAVE_REUSE = 19
+OPT_WAVE_REUSE, OPT_HOST_PIPE = 19, 20
 OPTIONS = {"solver": OPT_SOLVER, "split40": OPT_SPLIT40, "split40_batch": OPT_SPLIT40_BATCH,
            "search": OPT_SEARCH,
            "big_path": OPT_BIG_PATH, "big_batch": OPT_BIG_BATCH, "pageable": OPT_PAGEABLE,
@@ -38,11 +38,16 @@ OPTIONS = {"solver": OPT_SOLVER, "split40": OPT_SPLIT40, "split40_batch": OPT_SP
            "info_window": OPT_INFO_WINDOW, "index": OPT_INDEX,
            "record_reuse": OPT_RECORD_REUSE, "column_share": OPT_COLUMN_SHARE,
            "column_levels": OPT_COLUMN_LEVELS, "factor_reuse": OPT_FACTOR_REUSE,
-           "hit_merge": OPT_HIT_MERGE, "wave_reuse": OPT_WAVE_REUSE}
+           "hit_merge": OPT_HIT_MERGE, "wave_reuse": OPT_WAVE_REUSE,
+           "host_pipe": OPT_HOST_PIPE}
 
 #: cwbl_column_info_t.reason
 (COLUMN_SHARED, COLUMN_REASON_OFF, COLUMN_REASON_3D, COLUMN_REASON_Q1, COLUMN_REASON_NZ,
  COLUMN_REASON_PATH, COLUMN_REASON_GROUP, COLUMN_REASON_NO_TREES) = range(8)
+
+#: cwbl_transfer_info_t.reason
+(TRANSFER_PIPED, TRANSFER_REASON_OFF, TRANSFER_REASON_REGION, TRANSFER_REASON_REGISTER,
+ TRANSFER_REASON_BOUNCE) = range(5)
 
 ERRORS = {1: "CWBL_ERR_ARG", 2: "CWBL_ERR_STATE", 3: "CWBL_ERR_NO_DEVICE", 4: "CWBL_ERR_HIP",
           5: "CWBL_ERR_UNSUPPORTED", 6: "CWBL_ERR_OOM"}
@@ -138,13 +143,25 @@ class ColumnInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
 
 
+class TransferInfo(C.Structure):
+    _fields_ = [("host", C.c_int), ("piped", C.c_int), ("piped_back", C.c_int),
+                ("registered", C.c_int), ("bounce", C.c_int), ("reason", C.c_int),
+                ("tune_q_launches", C.c_longlong), ("bytes_piped_up", C.c_longlong),
+                ("bytes_piped_down", C.c_longlong), ("bytes_whole_up", C.c_longlong),
+                ("bytes_whole_down", C.c_longlong)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 #: exported symbols of the product library (include/cwb_letkf_core.h)
 EXPORTS = ["cwbl_init", "cwbl_set_stream", "cwbl_set_obs", "cwbl_analyze_var", "cwbl_analyze_vars",
            "cwbl_solve_batch", "cwbl_search",
            "cwbl_pack_columns", "cwbl_unpack_columns", "cwbl_pack_members",
            "cwbl_unpack_members", "cwbl_vcoord_mean", "cwbl_member_sum", "cwbl_scale", "cwbl_set_kernel_timing", "cwbl_kernel_times",
            "cwbl_set_option", "cwbl_bin_index", "cwbl_prep_info", "cwbl_reuse_info",
-           "cwbl_column_info", "cwbl_finalize", "cwbl_last_error", "cwbl_abi_version"]
+           "cwbl_column_info", "cwbl_transfer_info", "cwbl_finalize", "cwbl_last_error",
+           "cwbl_abi_version"]
 
 
 def _ptr(a):
@@ -330,6 +347,7 @@ def load_library(path=None):
     lib.cwbl_prep_info.argtypes = [C.POINTER(PrepInfo)]
     lib.cwbl_reuse_info.argtypes = [C.POINTER(ReuseInfo)]
     lib.cwbl_column_info.argtypes = [C.POINTER(ColumnInfo)]
+    lib.cwbl_transfer_info.argtypes = [C.POINTER(TransferInfo)]
     lib.cwbl_finalize.argtypes = []
     lib.cwbl_last_error.restype = cp
     lib.cwbl_abi_version.restype = C.c_int
@@ -339,7 +357,7 @@ def load_library(path=None):
                "cwbl_unpack_members", "cwbl_vcoord_mean",
                "cwbl_member_sum", "cwbl_scale", "cwbl_set_kernel_timing", "cwbl_kernel_times",
                "cwbl_set_option", "cwbl_bin_index", "cwbl_prep_info", "cwbl_reuse_info",
-               "cwbl_column_info", "cwbl_finalize"):
+               "cwbl_column_info", "cwbl_transfer_info", "cwbl_finalize"):
         getattr(lib, fn).restype = C.c_int
     return lib
 
@@ -477,6 +495,15 @@ class Core:
         "column_share" option, and if not why (ColumnInfo; reason: COLUMN_REASON_*)."""
         info = ColumnInfo()
         self._check(self.lib.cwbl_column_info(C.byref(info)))
+        return info
+
+    def transfer_info(self):
+        """cwbl_transfer_info: how the last analyze_var / analyze_vars moved a host slab's var
+        (TransferInfo): piped batch by batch or whole, the arrays page-locked for the call, the
+        bytes each way and, when a direction moved whole, why (reason: TRANSFER_REASON_*; the
+        "host_pipe" option)."""
+        info = TransferInfo()
+        self._check(self.lib.cwbl_transfer_info(C.byref(info)))
         return info
 
     # ---- member <-> column transposes (device pointers; see cwbl/transpose.py) ----------

@@ -86,6 +86,15 @@ module letkf_core_gpu
     ! cwbl_set_option: calls of one variable at k = 41..64 keep each point's factor for the next
     ! call with the same localisation (1; 0, default: off), within CWBL_OPT_RECORD_REUSE's budget
     integer(c_int), parameter, public :: CWBL_OPT_WAVE_REUSE = 19
+    ! cwbl_set_option: host-memory slabs of group calls, column-shared calls and calls with
+    ! tune_q = 1 travel batch by batch under the solves (1; 0, default: whole, around them)
+    integer(c_int), parameter, public :: CWBL_OPT_HOST_PIPE = 20
+    ! cwbl_transfer_info_t%reason
+    integer(c_int), parameter, public :: CWBL_TRANSFER_PIPED = 0
+    integer(c_int), parameter, public :: CWBL_TRANSFER_REASON_OFF = 1
+    integer(c_int), parameter, public :: CWBL_TRANSFER_REASON_REGION = 2
+    integer(c_int), parameter, public :: CWBL_TRANSFER_REASON_REGISTER = 3
+    integer(c_int), parameter, public :: CWBL_TRANSFER_REASON_BOUNCE = 4
 
     type, bind(C), public :: cwbl_bin_grid         ! cwbl_bin_index
         real(c_float)  :: x0, y0, z0, binv
@@ -108,6 +117,12 @@ module letkf_core_gpu
         integer(c_int)       :: levels, levels_per_wave, chunk_launches, reserved
     end type cwbl_column_info_t
 
+    type, bind(C), public :: cwbl_transfer_info_t  ! cwbl_transfer_info
+        integer(c_int)       :: host, piped, piped_back, registered, bounce, reason
+        integer(c_long_long) :: tune_q_launches, bytes_piped_up, bytes_piped_down
+        integer(c_long_long) :: bytes_whole_up, bytes_whole_down
+    end type cwbl_transfer_info_t
+
     ! projection_nml (module_config.f90:70-75), include/cwb_letkf_ingest.h
     type, bind(C), public :: cwbl_projection
         real(c_float) :: sta_lon, cen_lat, truelat1, truelat2
@@ -122,6 +137,7 @@ module letkf_core_gpu
               cwbl_vcoord_mean, &
               cwbl_member_sum, cwbl_scale, cwbl_set_stream, cwbl_set_option, &
               cwbl_bin_index, cwbl_prep_info, cwbl_reuse_info, cwbl_column_info, &
+              cwbl_transfer_info, &
               cwbl_finalize, cwbl_abi_version, cwbl_error, cwbl_check
     ! host obs ingest (include/cwb_letkf_ingest.h); file names and varname are passed as
     ! trim(name)//c_null_char
@@ -343,6 +359,12 @@ module letkf_core_gpu
             import :: c_int, cwbl_column_info_t
             type(cwbl_column_info_t), intent(out) :: info
         end function cwbl_column_info
+
+        ! how the last call moved a host slab's var (CWBL_OPT_HOST_PIPE)
+        integer(c_int) function cwbl_transfer_info(info) bind(C, name='cwbl_transfer_info')
+            import :: c_int, cwbl_transfer_info_t
+            type(cwbl_transfer_info_t), intent(out) :: info
+        end function cwbl_transfer_info
 
         integer(c_int) function cwbl_finalize() bind(C, name='cwbl_finalize')
             import :: c_int

@@ -197,7 +197,9 @@ typedef struct cwbl_stats {
   double    ms_search;       /* neighbour search kernels */
   double    ms_solve;        /* solve kernels (+ the tune_q pass when requested) */
   double    ms_copy;         /* host<->device copies of the slab (host memory only; for a */
-                             /* pageable slab: host time in its page-locked bounce copies) */
+                             /* pageable slab: host time in its page-locked bounce copies). */
+                             /* Piped transfers overlap the batches and are not counted, */
+                             /* those of CWBL_OPT_HOST_PIPE = 1 included */
 } cwbl_stats;
 
 int         cwbl_init(const cwbl_init_params *params);
@@ -400,7 +402,7 @@ enum {
                                 * its cached batches, 0 one launch per cached batch.
                                 * Bit-identical results either way.  Nothing that is cached
                                 * depends on it: setting it leaves a filled cache valid */
-  CWBL_OPT_WAVE_REUSE = 19     /* 1: cwbl_analyze_var on the one-wavefront path at k = 41..64
+  CWBL_OPT_WAVE_REUSE = 19,    /* 1: cwbl_analyze_var on the one-wavefront path at k = 41..64
                                 * (default solver) keeps each point's factor A = Q T Q^T for the
                                 * next call, within the CWBL_OPT_RECORD_REUSE budget (0 there
                                 * turns this cache off too): KP (KP - 1) / 2 + 5 KP fp64 words per
@@ -414,6 +416,22 @@ enum {
                                 * Accepted and ignored at k <= 16 and at k = 17..40 under
                                 * CWBL_OPT_SPLIT40 = 0.  Group calls and column-shared calls
                                 * neither read, fill nor invalidate the cache */
+  CWBL_OPT_HOST_PIPE = 20      /* host-memory slabs (CWBL_MEM_HOST) of the calls that otherwise
+                                * move var whole around the batches.  1: a group call
+                                * (cwbl_analyze_vars on a fused path) and a column-shared call
+                                * pipe var batch by batch as cwbl_analyze_var does, each
+                                * pageable var page-locked in place for the call; and a piped
+                                * call with tune_q = 1 (single calls included, through the
+                                * bounce slots too) runs tune_q_kernel over each batch right
+                                * behind its solve, so its analysis comes back batch by batch
+                                * as well.  A call still moves whole when the analysed region
+                                * is not the whole horizontal slab, when a registration fails,
+                                * or when CWBL_OPT_PAGEABLE = 1 meets a pageable var of a group
+                                * or a column-shared call (cwbl_transfer_info names the case).
+                                * 0 (default): every call moves its slab as without the
+                                * option.  Bit-identical results and equal counters either
+                                * way.  Nothing that is cached depends on it: setting it leaves
+                                * a filled cache valid */
 };
 int         cwbl_set_option(int option, long long value);
 
@@ -506,6 +524,37 @@ typedef struct cwbl_column_info_t {
   int       reserved;
 } cwbl_column_info_t;
 int         cwbl_column_info(cwbl_column_info_t *out);
+
+/* How the last cwbl_analyze_var (or cwbl_analyze_vars) moved its slab's var between host and
+ * device.  A CWBL_MEM_DEVICE call reports zeros.  The bytes are var's alone (x, y and alt are
+ * staged before the batches in every mode), summed over the variables of a group.  Where the
+ * variables of cwbl_analyze_vars run one after another, this is the last variable's call. */
+enum {
+  CWBL_TRANSFER_PIPED = 0,           /* nothing moved whole (also: device slab, nothing to do) */
+  CWBL_TRANSFER_REASON_OFF = 1,      /* CWBL_OPT_HOST_PIPE is 0: a group or column-shared call
+                                      * moved whole both ways, a single call with tune_q = 1
+                                      * came back whole */
+  CWBL_TRANSFER_REASON_REGION = 2,   /* ix_lim < nx or iy_lim < ny: a batch is no contiguous run */
+  CWBL_TRANSFER_REASON_REGISTER = 3, /* a group or column-shared call: hipHostRegister failed
+                                      * for a var (a locked-memory limit, for instance) */
+  CWBL_TRANSFER_REASON_BOUNCE = 4    /* CWBL_OPT_PAGEABLE = 1 with a pageable var of a group or
+                                      * column-shared call: those have no bounce-slot mode */
+};
+typedef struct cwbl_transfer_info_t {
+  int       host;             /* 1: the slab was CWBL_MEM_HOST */
+  int       piped;            /* 1: var went up batch by batch (S.h2d under the solves) */
+  int       piped_back;       /* 1: the analysis came back batch by batch */
+  int       registered;       /* var arrays page-locked in place for the call */
+  int       bounce;           /* 1: through the library's page-locked bounce slots */
+  int       reason;           /* CWBL_TRANSFER_REASON_* when a direction moved whole */
+  long long tune_q_launches;  /* tune_q_kernel launches: one per flagged variable, or one per
+                               * batch and flagged variable when the call tuned per batch */
+  long long bytes_piped_up;   /* var bytes moved batch by batch, host to device */
+  long long bytes_piped_down; /* ... and device to host */
+  long long bytes_whole_up;   /* var bytes moved before the first batch */
+  long long bytes_whole_down; /* ... and after the last */
+} cwbl_transfer_info_t;
+int         cwbl_transfer_info(cwbl_transfer_info_t *out);
 
 int         cwbl_finalize(void);
 const char *cwbl_last_error(void);
