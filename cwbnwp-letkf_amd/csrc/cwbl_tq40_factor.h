@@ -30,6 +30,31 @@ __device__ __forceinline__ long long touched(long long x) {
   return x;
 }
 
+// LEAN: sm.tq's rows, sm.qs and sm.qz stand in the order the twisted walk takes them: side 0's
+// rows 0 .. H-1, then side 1's rows KP-1 .. H, so that both sides step through them with the
+// same compile-time stride.  Word 1 of a slot is the coupling with the walk's row before it
+// (side 0: c(i-1, i); side 1: c(i, i+1)); the middle coupling c(H-1, H) is word 1 of row KP.
+template <int KP>
+__device__ __forceinline__ int tq40_walk_slot(int i) {
+  constexpr int H = KP / 2;
+  return i < H ? i : KP + H - 1 - i;
+}
+// the same for a row of the 16 from LO on (i < KP), and the row itself without LEAN
+template <int KP, bool LEAN, int LO>
+__device__ __forceinline__ int tq40_slot16(int i) {
+  constexpr int H = KP / 2;
+  if constexpr (!LEAN || LO + 15 < H) return i;
+  else if constexpr (LO >= H) return KP + H - 1 - i;
+  else return tq40_walk_slot<KP>(i);
+}
+// where T's off-diagonal word i = c(i-1, i) goes (word 0, which is 0, and the coupling of a
+// side's first row are never read)
+template <int KP>
+__device__ __forceinline__ int tq40_walk_cslot(int i) {
+  constexpr int H = KP / 2;
+  return i < H ? i : i == H ? KP : KP + H - i;
+}
+
 // The background gathers of a point, as loaded: member i = row i.  Branch-free, every address
 // valid: a lane past the batch reads member 0 of point 0, a row past k member 0 of its point
 // (tq40_factor_solve masks both to 0).  The hit issues these inside the factor's stream, so
@@ -56,7 +81,12 @@ __device__ __forceinline__ void tq40_load_xb(const SlabDev &slab, const long lon
 // AHEAD (the hit) changes the order of loads only, never an expression: the first round's
 // node is fetched before the replay and each later one a round ahead, and the walk reads row
 // t + 1 before d_{t-1}'s reciprocal.  That costs six VGPRs, which the fill does not have.
-template <int KP, bool AHEAD>
+// LEAN (the merged hit alone) changes where a value is kept and which lanes a select masks,
+// never an expression either: the replay leaves each step's reflector v (1 at row j + 1,
+// x scal below) where it found x (phase 1: sm.pv's column, phase 2: the column's registers),
+// and the back-transform takes it from there instead of forming the same product again; phase
+// 2's columns may hold any words on the rows above j + 1 (tq40_factor_hit's plain loads).
+template <int KP, bool AHEAD, bool LEAN = false>
 __device__ __forceinline__ void tq40_factor_solve(
     const SolveConsts &c, const SlabDev &slab, Tq40Smem<KP> &sm,
     double (&A)[Tq40Layout<KP>::NS][KP], const float (&xbv)[Tq40Layout<KP>::NV], const long long g0,
@@ -69,11 +99,31 @@ __device__ __forceinline__ void tq40_factor_solve(
   const int lp = l < J0 ? l : 0;
   const bool pre = l < J0;
   auto vrow = [&](int vs) { return tq40_vrow<KP>(l, vs); };
+  // slot of sm.tq, sm.qs and sm.qz of row i = vrow(vs), 0 where the lane has no such row
+  // (the row itself without LEAN)
+  auto vslot = [&](auto vv, int i) {
+    constexpr int vs = decltype(vv)::value;
+    if constexpr (!LEAN || vs == 0) return i < KP ? i : 0;  // (J0 <= H)
+    else return tq40_slot16<KP, true, J0 + 16 * (vs > 0 ? vs - 1 : 0)>(i);
+  };
+  static_assert(J0 <= H, "the prefix rows are side 0's");
   // the point's accepted count waits in LDS for the store at the end (row KP's word 3 is
   // unused; every lane of the row holds the same count): one register less across the solve
   int *const pkeep = reinterpret_cast<int *>(&sm.tq[q][KP][3]);
   *pkeep = ptot;
-  const double trace = tq40_trace(sm, q, l, k);
+  double trace;
+  if constexpr (LEAN) {  // tq40_trace through the slots
+    double tp = 0.0;
+    sfor<(KP + 15) / 16>([&](auto rr) {
+      constexpr int r = decltype(rr)::value;
+      const int i = l + 16 * r;
+      if (16 * r + 15 < KP || i < KP)
+        tp += i < k ? sm.tq[q][i < KP ? tq40_slot16<KP, true, 16 * r>(i) : 0][0] : 0.0;
+    });
+    trace = rsum16(tp);
+  } else {
+    trace = tq40_trace(sm, q, l, k);
+  }
 
   // ---- the quadrature rule of the point: T only ---------------------------------------------
   // (twin: this level loop and the walk's LDS offsets below are solve_tq40_kernel's)
@@ -96,11 +146,13 @@ __device__ __forceinline__ void tq40_factor_solve(
   auto lds = [&](unsigned off) { return *reinterpret_cast<const double *>(smb + off); };
   auto sts = [&](unsigned off, double v) { *reinterpret_cast<double *>(smb + off) = v; };
   const unsigned tq0 = (unsigned)(offsetof(SM, tq) + (size_t)q * sizeof(sm.tq[0])) +
-                       (side ? (KP - 1) * 32u : 0u);   // row 0 of the walk
+                       (LEAN ? (side ? H * 32u : 0u)
+                             : (side ? (KP - 1) * 32u : 0u));   // row 0 of the walk
   const unsigned dirb = side ? (unsigned)-32 : 32u;   // next row of the walk
   const unsigned csb = side ? 40u : 8u;  // coupling with the previous row of the walk
   const unsigned qs0 = (unsigned)(offsetof(SM, qs) + (size_t)q * sizeof(sm.qs[0])) +
-                       (side ? (KP - H) * 8u : (H - 1) * 8u);  // row H-1 of the walk
+                       (LEAN ? (side ? H * 8u : 0u)            // LEAN: row 0 of the walk
+                             : (side ? (KP - H) * 8u : (H - 1) * 8u));  // row H-1 of the walk
   const unsigned qz0 = (unsigned)(offsetof(SM, qz) + (size_t)q * sizeof(sm.qz[0]));
   const unsigned bdir = side ? 8u : (unsigned)-8;    // back-substitution: previous row
   const double sk = sqrt((double)(k - 1));
@@ -144,7 +196,7 @@ __device__ __forceinline__ void tq40_factor_solve(
   // ---- replay: x' <- Q^T x', the x' half of every step of solve_tq40_kernel ----------------
   sfor<J0>([&](auto jj) {  // phase 1's reflectors
     constexpr int j = decltype(jj)::value, J1 = j + 1;
-    const double *pj = sm.pv[q][j];
+    double *const pj = sm.pv[q][j];
     const double scal = pj[0], tau = sm.tau[q][j];
     double u2a;
     if constexpr (J1 < J0) u2a = rbcast<J1>(uxP);
@@ -168,7 +220,11 @@ __device__ __forceinline__ void tq40_factor_solve(
       if constexpr (J1 == J0 && r == 0) vr = l == 0 ? 1.0 : xs;
       else vr = xs;
       ux[r] = fma(-tau * s2, vr, ux[r]);
+      if constexpr (LEAN) pj[J0 + l + 16 * r] = vr;
     });
+    // LEAN: v over x, row by row; the lanes without a prefix row store into word 0, the scal
+    // this step has read, and the prefix rows <= j + 1 into their own unused words
+    if constexpr (LEAN) pj[lp] = vP;
   });
   sfor<KT - 2>([&](auto jj) {  // phase 2's reflectors
     constexpr int jl = decltype(jj)::value, j = J0 + jl;
@@ -184,7 +240,8 @@ __device__ __forceinline__ void tq40_factor_solve(
       constexpr int r = decltype(rr)::value;
       if constexpr (16 * r + 15 > J1) {
         const int t = l + 16 * r;
-        if constexpr (r == R1) x[r] = t == J1 ? 0.0 : A[r][j];
+        if constexpr (r == R1 && LEAN) x[r] = t > J1 ? A[r][j] : 0.0;
+        else if constexpr (r == R1) x[r] = t == J1 ? 0.0 : A[r][j];
         else x[r] = A[r][j];
         xu = fma(x[r], ux[r], xu);
       } else {
@@ -199,12 +256,13 @@ __device__ __forceinline__ void tq40_factor_solve(
       const double xs = x[r] * scal;
       const double vr = t == J1 ? 1.0 : xs;
       ux[r] = fma(-tau * s2, vr, ux[r]);
+      if constexpr (LEAN && 16 * r + 15 > J1) A[r][j] = vr;
     });
   });
   if (pre) sm.tq[q][l][3] = uxP;
   sfor<NS>([&](auto rr) {
     constexpr int r = decltype(rr)::value;
-    sm.tq[q][J0 + l + 16 * r][3] = ux[r];
+    sm.tq[q][tq40_slot16<KP, LEAN, J0 + 16 * r>(J0 + l + 16 * r)][3] = ux[r];
   });
   __syncthreads();
 
@@ -231,23 +289,30 @@ __device__ __forceinline__ void tq40_factor_solve(
     // reciprocal, so that the LDS round trip runs under the rcp64 chain (rows 1 .. H-1 only:
     // never past the walk); otherwise it is row t, one register triple less.
     double nd, nc, ng;
-    auto next_row = [&]() {
-      pw += dirb;
-      nd = lds(pw);
-      nc = lds(pw + csb);
-      ng = lds(pw + 24);
+    auto next_row = [&](auto ww) {
+      if constexpr (LEAN) {  // walk row ww: the slots are in walk order, the base stays
+        constexpr unsigned wo = 32u * (unsigned)decltype(ww)::value;
+        nd = lds(pw + wo);
+        nc = lds(pw + wo + 8);
+        ng = lds(pw + wo + 24);
+      } else {
+        pw += dirb;
+        nd = lds(pw);
+        nc = lds(pw + csb);
+        ng = lds(pw + 24);
+      }
     };
-    if constexpr (AHEAD) next_row();
+    if constexpr (AHEAD) next_row(std::integral_constant<int, 1>{});
     sfor<H - 1>([&](auto tt) {
       constexpr int t = decltype(tt)::value + 1;
       if constexpr (!AHEAD) {
         asm volatile("" : "+v"(pw) : "v"(dl));
-        next_row();
+        next_row(std::integral_constant<int, t>{});
       }
       const double dt = nd, ct = nc, g = ng;
       if constexpr (AHEAD && t < H - 1) {
         asm volatile("" : "+v"(pw) : "v"(dl));
-        next_row();
+        next_row(std::integral_constant<int, t + 1>{});
       }
       const double rdl = rcp64(dl);
       const double lt = ct * rdl;
@@ -257,39 +322,50 @@ __device__ __forceinline__ void tq40_factor_solve(
       gt = fma(-lt, gt, g);
     });
     // rows H-1 (top) and H (bottom): 2x2 solve with the partner lane's pivot
-    const double cm = T[H][1];
+    const double cm = T[LEAN ? KP : H][1];
     const double dlo = ror8(dl), go = ror8(gt);
     double xv = (gt * dlo - cm * go) / fma(dl, dlo, -cm * cm);
     const bool last = round == R - 1;
     const bool zlane = last && n8 == 7;  // T^-1 u2: not a node of the sum
     const double om = zlane ? 0.0 : omega;
-    unsigned ps = qs0;                          // qs of the walk's current row
-    unsigned pz = qz0 + (zlane ? qs0 - (unsigned)offsetof(SM, qs) - (unsigned)q * KP * 8u
-                               : KP * 8u);     // qz of that row, or the dump word
+    unsigned ps = qs0;                          // qs of the walk's current row (LEAN: row 0)
+    // qz of that row, or the dump word.  LEAN has no dump: a lane that is not the z lane puts
+    // its x where the side's sum goes, and the sum's store, which follows, overwrites it
+    unsigned pz = LEAN ? (zlane ? qz0 + (side ? H * 8u : 0u) : qs0)
+                       : qz0 + (zlane ? qs0 - (unsigned)offsetof(SM, qs) - (unsigned)q * KP * 8u
+                                      : KP * 8u);
     const unsigned zdir = zlane ? bdir : 0u;
-    auto emit = [&](double x) {
+    auto emit = [&](double x, auto ww) {
       double s = om * x;
       s += dpp_f64<0xB1>(s);   // quad_perm [1,0,3,2]
       s += dpp_f64<0x4E>(s);   // quad_perm [2,3,0,1]
       s += dpp_f64<0x141>(s);  // row_half_mirror: the 8 lanes of the side
       // stores without branches: the side's 8 lanes store the same sum
-      sts(ps, s);
-      sts(pz, x);
+      if constexpr (LEAN) {
+        constexpr unsigned wo = 8u * (unsigned)decltype(ww)::value;
+        sts(pz + wo, x);
+        sts(ps + wo, s);
+      } else {
+        sts(ps, s);
+        sts(pz, x);
+      }
     };
-    emit(xv);
+    emit(xv, std::integral_constant<int, H - 1>{});
     sfor<H - 1>([&](auto tt) {
       constexpr int t = H - 2 - decltype(tt)::value;
       xv = fma(-mm[t], xv, hh[t]);
-      ps += bdir;
-      pz += zdir;
+      if constexpr (!LEAN) {
+        ps += bdir;
+        pz += zdir;
+      }
       asm volatile("" : "+v"(ps), "+v"(pz) : "v"(xv));
-      emit(xv);
+      emit(xv, std::integral_constant<int, t>{});
     });
     __syncthreads();
     sfor<NV>([&](auto vv) {
       constexpr int vs = decltype(vv)::value;
       const int i = vrow(vs);
-      const int ic = i < KP ? i : 0;
+      const int ic = vslot(vv, i);
       ys[vs] += i < KP ? sm.qs[q][ic] : 0.0;
       if (last) z[vs] = i < KP ? sm.qz[q][ic] : 0.0;
     });
@@ -300,7 +376,7 @@ __device__ __forceinline__ void tq40_factor_solve(
     constexpr int vs = decltype(vv)::value;
     const int i = vrow(vs);
     // ((Q^T b1)_i from LDS: kept in registers it would be live across the quadrature)
-    const double u1 = sm.tq[q][i < KP ? i : 0][2];
+    const double u1 = sm.tq[q][vslot(vv, i)][2];
     dpart = i < KP ? fma(u1, z[vs], dpart) : dpart;
   });
   const double d = rsum16(dpart);
@@ -314,7 +390,8 @@ __device__ __forceinline__ void tq40_factor_solve(
     constexpr int jl = KT - 3 - decltype(jj)::value, j = J0 + jl, J1 = jl + 1;
     constexpr int R1 = J1 / 16, L1 = J1 % 16;
     const double tj = sm.tau[q][j];
-    const double scal = rbcast<L1>(A[R1][j]);
+    double scal;
+    if constexpr (!LEAN) scal = rbcast<L1>(A[R1][j]);
     double vv[NS], a = 0.0;
     sfor<NS>([&](auto rr) {
       constexpr int r = decltype(rr)::value;
@@ -322,8 +399,12 @@ __device__ __forceinline__ void tq40_factor_solve(
         const int t = lb + 16 * r;
         // column j's registers hold x, which is 0 on the rows < j + 1 (scal at row j + 1),
         // in the slots that step j wrote: the reflector is 1 at row j + 1 and x scal below
-        if constexpr (16 * r + 15 > J1) vv[r] = t == J1 ? 1.0 : A[r][j] * scal;
-        else vv[r] = t == J1 ? 1.0 : 0.0;
+        if constexpr (16 * r + 15 > J1) {
+          if constexpr (LEAN) vv[r] = A[r][j];  // the replay's v
+          else vv[r] = t == J1 ? 1.0 : A[r][j] * scal;
+        } else {
+          vv[r] = t == J1 ? 1.0 : 0.0;
+        }
         a = fma(vv[r], y[r + 1], a);
       } else {
         vv[r] = 0.0;
@@ -339,15 +420,26 @@ __device__ __forceinline__ void tq40_factor_solve(
     constexpr int j = J0 - 1 - decltype(jj)::value, J1 = j + 1;
     const double tj = sm.tau[q][j];
     const double *pj = sm.pv[q][j];
-    const double scal = pj[0];
-    const double v0 = lb == J1 ? 1.0 : (lb < J0 && lb > J1) ? pj[lb] * scal : 0.0;  // 0 at rows <= j + 1
+    double scal, v0;
+    if constexpr (!LEAN) {
+      scal = pj[0];
+      v0 = lb == J1 ? 1.0 : (lb < J0 && lb > J1) ? pj[lb] * scal : 0.0;  // 0 at rows <= j + 1
+    } else if constexpr (J1 == J0) {
+      v0 = lb == J1 ? 1.0 : 0.0;
+    } else {
+      v0 = (lb < J0 && lb >= J1) ? pj[lb] : 0.0;  // the replay's v
+    }
     double vv[NS];
     double a = v0 * y[0];
     sfor<NS>([&](auto rr) {
       constexpr int r = decltype(rr)::value;
-      const double pr = pj[J0 + lb + 16 * r] * scal;
-      if constexpr (J1 == J0 && r == 0) vv[r] = lb == 0 ? 1.0 : pr;
-      else vv[r] = pr;
+      if constexpr (LEAN) {
+        vv[r] = pj[J0 + lb + 16 * r];
+      } else {
+        const double pr = pj[J0 + lb + 16 * r] * scal;
+        if constexpr (J1 == J0 && r == 0) vv[r] = lb == 0 ? 1.0 : pr;
+        else vv[r] = pr;
+      }
       a = fma(vv[r], y[r + 1], a);
     });
     a = rsum16(a);
@@ -428,7 +520,8 @@ __device__ __forceinline__ void tq40_factor_solve(
 // Block b of the nblk that cover the npts points from g0 (records ws, entries aux, info as of
 // launch_solve_tq40_factor): the whole of solve_tq40_factor_kernel, and of a segment's block
 // of solve_tq40_factor_merged_kernel.
-template <int KP>
+// LEAN: the merged kernel's variant (tq40_factor_solve's, and plain loads of phase 2's columns).
+template <int KP, bool LEAN = false>
 __device__ __forceinline__ void tq40_factor_hit(const SolveConsts &c, const SlabDev &slab,
                                                 const long long g0,
                                                 const int npts, const double *__restrict__ ws,
@@ -536,7 +629,9 @@ __device__ __forceinline__ void tq40_factor_hit(const SolveConsts &c, const Slab
         A[r][j] = rw(rl, (unsigned)(FR::col(j) + 16 * r - J1));
       } else if constexpr (16 * r + 15 >= J1) {  // the rows above j + 1 are 0
         const int t = l + 16 * r;
-        A[r][j] = rwb(rec_off(t >= J1, (int)rq + t - J1), (unsigned)FR::col(j));
+        // (LEAN: or words of the columns before, in the same record, which the replay masks)
+        if constexpr (LEAN) A[r][j] = rw(rl, (unsigned)(FR::col(j) + 16 * r - J1));
+        else A[r][j] = rwb(rec_off(t >= J1, (int)rq + t - J1), (unsigned)FR::col(j));
       }
     });
   });
@@ -545,21 +640,24 @@ __device__ __forceinline__ void tq40_factor_hit(const SolveConsts &c, const Slab
   sfor<(KP + 15) / 16>([&](auto rr) {
     constexpr int r = decltype(rr)::value;
     const int i = l + 16 * r;
-    sm.tq[q][i < KP ? i : KP][0] = dg[r];  // (row KP's words 0, 2, 3 are unused: the dump)
+    // (row KP's words 0, 2, 3 are unused: the dump)
+    sm.tq[q][i < KP ? tq40_slot16<KP, LEAN, 16 * r>(i) : KP][0] = dg[r];
   });
   sm.tq[q][pre ? l : KP][2] = ubP;
   sfor<NS>([&](auto rr) {
     constexpr int r = decltype(rr)::value;
-    sm.tq[q][J0 + l + 16 * r][2] = ub[r];
+    sm.tq[q][tq40_slot16<KP, LEAN, J0 + 16 * r>(J0 + l + 16 * r)][2] = ub[r];
   });
   // T's off-diagonal (word 0 is 0, word KP-1 the trailing 2 x 2's) and tau as the fill's steps
   // left them in LDS; row KP's off-diagonal closes the walk from the bottom
   sfor<NA>([&](auto rr) {
     constexpr int r = decltype(rr)::value;
-    sm.tq[q][arow(r)][1] = bt[r];
+    sm.tq[q][LEAN ? tq40_walk_cslot<KP>(arow(r)) : arow(r)][1] = bt[r];
     sm.tau[q][arow(r)] = ta[r];
   });
-  sm.tq[q][KP][1] = 0.0;  // (every lane of the row stores the same value: no branch)
+  // (every lane of the row stores the same value: no branch; LEAN keeps c(H-1, H) there, and
+  // the coupling above side 1's first row is never read)
+  if constexpr (!LEAN) sm.tq[q][KP][1] = 0.0;
 
   // ---- the reflectors, where solve_tq40_multi_kernel keeps them -----------------------------------
   // phase 1: sm.pv[q][j] holds x by row and the step's scal in word 0, which the lanes without
@@ -575,7 +673,7 @@ __device__ __forceinline__ void tq40_factor_hit(const SolveConsts &c, const Slab
   });
   __syncthreads();
 
-  tq40_factor_solve<KP, true>(c, slab, sm, A, xv, g0, valid, ptot, gi, q, l, info);
+  tq40_factor_solve<KP, true, LEAN>(c, slab, sm, A, xv, g0, valid, ptot, gi, q, l, info);
 }
 
 }  // namespace cwbl

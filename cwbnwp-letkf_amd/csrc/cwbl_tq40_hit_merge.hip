@@ -14,6 +14,9 @@ namespace cwbl {
 // the 32-bit ones.  The XCD order is taken per segment, as that launch would (over the whole
 // grid it measured 0.3 % slower).  Working the segment out from the batch size instead of
 // loading it, where the batches are equal, measured the same as the load.
+// The block is the LEAN form of that text (cwbl_tq40_factor.h): the same expressions on the
+// same bits with fewer VALU instructions around them (profiles/hit_lean.txt); the per-batch
+// kernel and the fill keep the plain form and their register figures.
 template <int KP>
 __global__ void __launch_bounds__(64, 2)
 solve_tq40_factor_merged_kernel(SolveConsts c, SlabDev slab, const HitSeg *__restrict__ seg,
@@ -22,9 +25,10 @@ solve_tq40_factor_merged_kernel(SolveConsts c, SlabDev slab, const HitSeg *__res
   const HitSeg sg = seg[blockIdx.y];
   const int nblk = (sg.ns + 3) >> 2;
   if ((int)blockIdx.x >= nblk) return;  // (the whole block: a row is as wide as the largest segment)
-  tq40_factor_hit<KP>(c, slab, sg.g0, sg.ns, ws + (size_t)sg.ord * FactorRecord<KP>::WORDS,
-                      aux + (size_t)sg.ord * FactorAux<KP>::WORDS, info + sg.info, blockIdx.x,
-                      nblk);
+  tq40_factor_hit<KP, true>(c, slab, sg.g0, sg.ns,
+                            ws + (size_t)sg.ord * FactorRecord<KP>::WORDS,
+                            aux + (size_t)sg.ord * FactorAux<KP>::WORDS, info + sg.info,
+                            blockIdx.x, nblk);
 }
 
 hipError_t launch_solve_tq40_factor_merged(hipStream_t s, int kp, SolveConsts c, SlabDev slab,
