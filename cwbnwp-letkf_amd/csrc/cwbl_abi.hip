@@ -224,7 +224,7 @@ struct TreeBufs {
 enum KernelId {
   KT_SEARCH_BINNED, KT_SEARCH_FLAGGED, KT_SEARCH_TREE, KT_ASSEMBLE_RECORD, KT_SOLVE_TQ40,
   KT_SOLVE_TQ40_MULTI, KT_SOLVE_TQ40_COLUMN, KT_FILL_TQ40_FACTOR, KT_SOLVE_TQ40_FACTOR, KT_SOLVE_TQ_MULTI2, KT_SOLVE_TQ_MULTI4, KT_SOLVE_TQ_MULTI8,
-  KT_BIG_HANDOFF, KT_TQB_TAIL, KT_BIG_HANDOFF_MULTI2, KT_BIG_HANDOFF_MULTI4,
+  KT_BIG_HANDOFF, KT_TQB_TAIL, KT_FILL_TQB_TAIL, KT_SOLVE_TQB_FACTOR, KT_BIG_HANDOFF_MULTI2, KT_BIG_HANDOFF_MULTI4,
   KT_BIG_HANDOFF_MULTI8, KT_TQB_TAIL_MULTI2, KT_TQB_TAIL_MULTI4, KT_TQB_TAIL_MULTI8,
   KT_SOLVE_TQ, KT_FILL_TQ_WAVE, KT_SOLVE_TQ_WAVE_FACTOR, KT_SOLVE_TQ_BIG, KT_SOLVE_JACOBI,
   KT_TUNE_Q,
@@ -249,6 +249,11 @@ struct KTime { long long launches = 0, points = 0; double ms = 0.0; };
 // leaves each cached point's WaveFactor<KP> in the batch's region; a hit runs
 // solve_tq_wave_factor_kernel on those and nothing before it.  One record is one factor (`words`),
 // steps' scalars included: the budget bounds all of it, and there is no FactorAux.
+// Big reuse (CWBL_OPT_BIG_REUSE): the same cache on the hand-off path at KP = 96.  A fill runs the
+// hand-off kernel unchanged and fill_tqb_tail_kernel in the tail's place, which leaves each cached
+// point's BigFactor<96, 32> in the batch's region; a hit runs solve_tqb_factor_kernel on those and
+// nothing before it, one launch per sub-batch (CWBL_OPT_BIG_BATCH).  As with wave reuse one
+// record is one factor, inside the budget, and there is no FactorAux.
 struct RecordKey {
   unsigned long long gen;  // State::gen: obs set, cwbl_init constants, options
   int kp;                  // the path's KP (the record path: kTq4KP)
@@ -268,8 +273,10 @@ struct RecordCache {
   // ordinal: batch b's entries start at entry off[b] / WORDS, sub-batch s0's s0 entries on.
   DevBuf rec, aux, info, sx, sy, salt, flag;
   PinBuf hflag;
-  size_t words = AsmRecord<kTq4KP>::WORDS;  // fp64 words of a record: AsmRecord or WaveFactor
+  size_t words = AsmRecord<kTq4KP>::WORDS;  // fp64 words of a record: AsmRecord, WaveFactor or
+                                             // BigFactor
   bool wave = false;                         // the allocation last served the one-wavefront path
+  bool big = false;                          // ... the hand-off path
   std::vector<std::pair<long long, int>> plan;
   std::vector<size_t> off;
   long long pts = 0;
@@ -281,6 +288,7 @@ struct RecordCache {
   void release() {
     valid = false;
     wave = false;
+    big = false;
     for (DevBuf *b : {&rec, &aux, &info, &sx, &sy, &salt, &flag}) b->release();
     hflag.release();
     plan.clear();
@@ -352,6 +360,7 @@ struct State {
   bool factor_reuse = true;       // CWBL_OPT_FACTOR_REUSE: the cache keeps factors, not records
   bool hit_merge = true;          // CWBL_OPT_HIT_MERGE: one hit launch per info window
   bool wave_reuse = false;        // CWBL_OPT_WAVE_REUSE: the factor cache of k = 41..64
+  bool big_reuse = false;         // CWBL_OPT_BIG_REUSE: the factor cache of k = 65..96
   bool host_pipe = false;         // CWBL_OPT_HOST_PIPE: group, column-shared and tune_q calls
                                   // pipe their host slabs per batch
   // the segment tables of a call's merged hit launches (HitSeg): written by the host, one
@@ -523,6 +532,10 @@ std::string kernel_name(int id) {
     case KT_TQB_TAIL:
       return "solve_tqb_tail_kernel<" + kp + ", " + std::to_string(big_split_j0(S.kp)) +
              (S.kp == 128 ? ", 3>" : ", 2>");
+    case KT_FILL_TQB_TAIL:
+      return "fill_tqb_tail_kernel<" + kp + ", " + std::to_string(big_split_j0(S.kp)) + ">";
+    case KT_SOLVE_TQB_FACTOR:
+      return "solve_tqb_factor_kernel<" + kp + ", " + std::to_string(big_split_j0(S.kp)) + ">";
     case KT_BIG_HANDOFF_MULTI2:
     case KT_BIG_HANDOFF_MULTI4:
     case KT_BIG_HANDOFF_MULTI8: {
@@ -1110,6 +1123,9 @@ bool handoff_path() {
 // the one-wavefront path's calls that fill and read the factor cache (CWBL_OPT_WAVE_REUSE;
 // accepted and ignored at the smaller KP)
 bool wave_reuse_path() { return S.wave_reuse && wave_path() && S.kp > kTq4KP; }
+// the hand-off path's calls that fill and read the factor cache (CWBL_OPT_BIG_REUSE; accepted
+// and ignored at KP = 128 and on every other path)
+bool big_reuse_path() { return S.big_reuse && handoff_path() && S.kp == 96; }
 
 void make_record_key(RecordKey &key, const cwbl_var_params *vp, const cwbl_slab *sl) {
   std::memset(&key, 0, sizeof key);
@@ -1153,7 +1169,10 @@ int begin_fill(VarCall &v, const RecordKey &key) {
   C.off.clear();
   C.pts = 0;
   C.wave = wave_reuse_path();
-  C.words = C.wave ? wave_factor_words(S.kp) : (size_t)AsmRecord<kTq4KP>::WORDS;
+  C.big = big_reuse_path();
+  C.words = C.wave  ? wave_factor_words(S.kp)
+            : C.big ? big_factor_words(S.kp)
+                    : (size_t)AsmRecord<kTq4KP>::WORDS;
   size_t words = 0;
   for (const auto &b : v.plan) {
     // (+1: the spare record; the wave kernels read none, the region's layout is one)
@@ -1175,7 +1194,7 @@ int begin_fill(VarCall &v, const RecordKey &key) {
             C.rec.ensure(std::min(S.reuse_budget, need + need / 16)) == hipSuccess;
   // The steps' scalars of the factors, an entry per record: beside the budget's cut, like info
   // and the snapshot, with the same headroom; a cache of records holds none
-  if (S.factor_reuse && !C.wave) {
+  if (S.factor_reuse && !C.wave && !C.big) {
     const size_t aneed =
         words / AsmRecord<kTq4KP>::WORDS * FactorAux<kTq4KP>::WORDS * sizeof(double);
     ok = ok && (aneed <= C.aux.n || C.aux.ensure(aneed + aneed / 16) == hipSuccess);
@@ -1655,7 +1674,10 @@ long long sub_batch(int nb, long long cap) {
 // assembles into and a hit (no lists, no assembly) solves from; null: S.wsa.  caux: that
 // region's FactorAux entries (a cached batch under factor reuse; else null and unused).  On the
 // one-wavefront path crec is the batch's region of WaveFactors (CWBL_OPT_WAVE_REUSE): a fill
-// runs fill_tq_wave_kernel in solve_tq_kernel's place, a hit solve_tq_wave_factor_kernel.
+// runs fill_tq_wave_kernel in solve_tq_kernel's place, a hit solve_tq_wave_factor_kernel.  On
+// the hand-off path it is the batch's region of BigFactors (CWBL_OPT_BIG_REUSE), every
+// sub-batch's: a fill runs fill_tqb_tail_kernel in the tail's place, a hit
+// solve_tqb_factor_kernel alone.
 int solve_batch_path(VarCall &v, long long g0, int nb, const int *ncnt, const int *nidx,
                      int2 *infob, hipEvent_t b2, hipEvent_t dn, double *crec = nullptr,
                      bool hit = false, double *caux = nullptr) {
@@ -1732,10 +1754,19 @@ int solve_batch_path(VarCall &v, long long g0, int nb, const int *ncnt, const in
     const long long fit = std::max<long long>(
         kListLanes, (long long)(S.handoff_budget / rec_bytes) / kListLanes * kListLanes);
     const long long Bs = sub_batch(nb, std::min<long long>(S.big_sub, fit));
-    HIPCHK(S.wsa.ensure((size_t)Bs * rec_bytes));
+    // a cached batch of the factor cache: sub-batch s0 starts s0 factors into its region
+    const bool bigf = crec && !v.group;
+    const size_t fwords = big_factor_words(S.kp);
+    if (!(bigf && hit)) HIPCHK(S.wsa.ensure((size_t)Bs * rec_bytes));
     for (long long s0 = 0; s0 < nb; s0 += Bs) {
       const int ns = (int)std::min<long long>(Bs, nb - s0);
       HIPCHK(kt_begin(S.stream, &kt));
+      if (bigf && hit) {
+        HIPCHK(launch_solve_tqb_factor(S.stream, S.kp, c, sd, g0 + s0, ns,
+                                       crec + (size_t)s0 * fwords, infob + s0));
+        HIPCHK(kt_end(S.stream, kt, KT_SOLVE_TQB_FACTOR, ns));
+        continue;
+      }
       if (v.group) {
         HIPCHK(launch_big_handoff_multi(S.stream, S.kp, dtrees, c, sd, v.tv, g0 + s0, ns,
                                         ncnt + s0 * nt, nidx + s0 * list_cap, infob + s0,
@@ -1751,6 +1782,12 @@ int solve_batch_path(VarCall &v, long long g0, int nb, const int *ncnt, const in
                                 nidx + s0 * list_cap, infob + s0, S.wsa.as<double>()));
       HIPCHK(kt_end(S.stream, kt, KT_BIG_HANDOFF, ns));
       HIPCHK(kt_begin(S.stream, &kt));
+      if (bigf) {
+        HIPCHK(launch_fill_tqb_tail(S.stream, S.kp, c, sd, g0 + s0, ns, S.wsa.as<double>(),
+                                    infob + s0, crec + (size_t)s0 * fwords));
+        HIPCHK(kt_end(S.stream, kt, KT_FILL_TQB_TAIL, ns));
+        continue;
+      }
       HIPCHK(launch_solve_tqb_tail(S.stream, S.kp, c, sd, g0 + s0, ns, S.wsa.as<double>(),
                                    infob + s0));
       HIPCHK(kt_end(S.stream, kt, KT_TQB_TAIL, ns));
@@ -2070,6 +2107,7 @@ int cwbl_init(const cwbl_init_params *p) {
   S.factor_reuse = true;
   S.hit_merge = true;
   S.wave_reuse = false;
+  S.big_reuse = false;
   S.host_pipe = false;
   S.ncu = prop.multiProcessorCount;
   std::memset(&P, 0, sizeof P);
@@ -2177,6 +2215,11 @@ int cwbl_set_option(int option, long long value) {
       if (!range(0, 1)) break;
       S.wave_reuse = value == 1;
       if (S.cache.wave) S.cache.release();  // off holds no memory (a record cache keeps its own)
+      return CWBL_OK;
+    case CWBL_OPT_BIG_REUSE:
+      if (!range(0, 1)) break;
+      S.big_reuse = value == 1;
+      if (S.cache.big) S.cache.release();  // off holds no memory
       return CWBL_OK;
     default:
       return fail(CWBL_ERR_ARG, "cwbl_set_option: unknown option %d", option);
@@ -2452,7 +2495,7 @@ static int analyze_call(VarCall &v, cwbl_stats *stats) {
   CI.reason = column_reason(v);
   const bool col_candidate = CI.reason == CWBL_COLUMN_SHARED;
   const bool reuse_on =
-      !v.group && !col_candidate && (record_path() || wave_reuse_path()) &&
+      !v.group && !col_candidate && (record_path() || wave_reuse_path() || big_reuse_path()) &&
       S.reuse_budget > 0 && npts > 0;
   RecordKey key;
   bool staged = false;
@@ -2556,7 +2599,7 @@ static int analyze_call(VarCall &v, cwbl_stats *stats) {
     double *const crec = bi < v.ncached ? C.rec.as<double>() + C.off[bi] : nullptr;
     const size_t aoff = crec ? C.off[bi] / C.words * FactorAux<kTq4KP>::WORDS : 0;
     double *const caux =
-        crec && S.factor_reuse && !C.wave ? C.aux.as<double>() + aoff : nullptr;
+        crec && S.factor_reuse && !C.wave && !C.big ? C.aux.as<double>() + aoff : nullptr;
     const bool hit = crec && v.reuse == 2;
     if (hit && v.merge) {
       // the cached batches of this window: [bi, be)

@@ -458,6 +458,43 @@ hipError_t launch_fill_tq_wave(hipStream_t s, int kp, const TreeDesc *trees, Sol
 hipError_t launch_solve_tq_wave_factor(hipStream_t s, int kp, SolveConsts c, SlabDev slab,
                                        long long g0, int npts, const double *fac, int2 *info);
 
+// The factor cache of the hand-off path at KP = 96 (CWBL_OPT_BIG_REUSE, cwbl_tq_big_factor.hip).
+// What it keeps of a point, in fp64 words, every one the bits the fill's kernel pair produced:
+// T's diagonal and off-diagonal, Q^T b1, tau_j and (steps j >= J0) scal_j as the tail's sm.tq,
+// sm.tau and sm.scl hold them after its loop; the hand-off kernel's reflectors j < J0 as it
+// forms them (v_j = x scal with 1 at row j + 1: BigHandoff::HV), rows j + 1 .. KP-1; the tail's
+// columns j >= J0 as the raw pivot row x (BigHandoff::BT), rows j + 2 .. KP-1.  The two halves
+// differ because the kernels do: the hand-off kernel sums v . x', the tail scal (x . x') + x'_{j+1}.
+// A column's rows are consecutive words, one per lane.
+template <int KP, int J0>
+struct BigFactor {
+  static constexpr int KT = KP - J0;
+  static constexpr int D = 0;           // d_i (KP)
+  static constexpr int C = KP;          // c(i-1, i) as sm.tq[i][1]: 0 at i = 0 (KP)
+  static constexpr int U1 = 2 * KP;     // Q^T b1 (KP)
+  static constexpr int TAU = 3 * KP;    // tau_j (KP)
+  static constexpr int SCAL = 4 * KP;   // scal_j, j = J0 .. k-3 (KP; the others unwritten)
+  static constexpr int HV = 5 * KP;     // the hand-off kernel's reflectors
+  // row j + 1 of reflector j < J0; row i >= j + 1 at hv(j) + i - (j + 1)
+  __host__ __device__ static constexpr int hv(int j) { return HV + j * (KP - 1) - j * (j - 1) / 2; }
+  static constexpr int BT = hv(J0);     // the tail's columns
+  // row J0 + jl + 2 of the tail's step jl (j = J0 + jl); row J0 + l, l >= jl + 2, at
+  // bt(jl) + l - (jl + 2)
+  __host__ __device__ static constexpr int bt(int jl) {
+    return BT + jl * (KT - 2) - jl * (jl - 1) / 2;
+  }
+  static constexpr int WORDS = bt(KT - 2);
+};
+static_assert(BigFactor<96, 32>::WORDS <= 96 * 95 / 2 + 5 * 96, "the factor's bound");
+constexpr size_t big_factor_words(int kp) { return kp == 96 ? BigFactor<96, 32>::WORDS : 0; }
+// fill: launch_solve_tqb_tail on the hand-off kernel's records `ws`, which also leaves the npts
+// factors at `fac`; the hit: the same analysis from them and from info[i].x = p of the fill (no
+// lists, no trees, no hand-off kernel, no records).  KP = 96 only.
+hipError_t launch_fill_tqb_tail(hipStream_t s, int kp, SolveConsts c, SlabDev slab, long long g0,
+                                int npts, double *ws, int2 *info, double *fac);
+hipError_t launch_solve_tqb_factor(hipStream_t s, int kp, SolveConsts c, SlabDev slab,
+                                   long long g0, int npts, const double *fac, int2 *info);
+
 // KP = 96, 128: one 256-thread workgroup per point (cwbl_tq_big.hip)
 hipError_t launch_solve_tq_big(hipStream_t s, int kp, bool assembled, const TreeDesc *trees,
                                SolveConsts c, SlabDev slab, long long g0, int npts,

@@ -416,7 +416,7 @@ enum {
                                 * Accepted and ignored at k <= 16 and at k = 17..40 under
                                 * CWBL_OPT_SPLIT40 = 0.  Group calls and column-shared calls
                                 * neither read, fill nor invalidate the cache */
-  CWBL_OPT_HOST_PIPE = 20      /* host-memory slabs (CWBL_MEM_HOST) of the calls that otherwise
+  CWBL_OPT_HOST_PIPE = 20,     /* host-memory slabs (CWBL_MEM_HOST) of the calls that otherwise
                                 * move var whole around the batches.  1: a group call
                                 * (cwbl_analyze_vars on a fused path) and a column-shared call
                                 * pipe var batch by batch as cwbl_analyze_var does, each
@@ -432,6 +432,23 @@ enum {
                                 * option.  Bit-identical results and equal counters either
                                 * way.  Nothing that is cached depends on it: setting it leaves
                                 * a filled cache valid */
+  CWBL_OPT_BIG_REUSE = 21      /* 1: cwbl_analyze_var on the hand-off path at k = 65..96 (KP = 96,
+                                * default solver, CWBL_OPT_BIG_PATH = 1) keeps each point's
+                                * factor A = Q T Q^T for the next call, within the
+                                * CWBL_OPT_RECORD_REUSE budget (0 there turns this cache off
+                                * too): at most KP (KP - 1) / 2 + 5 KP fp64 words per point
+                                * (4977 words, 39.8 KB).  A later call with an equal key (the
+                                * record cache's, and KP) and bit-equal coordinates runs no obs
+                                * preparation, search, assembly, hand-off kernel or
+                                * tridiagonalisation: one solve_tqb_factor_kernel per cached
+                                * sub-batch (CWBL_OPT_BIG_BATCH).  Bit-identical results and
+                                * equal counters; reported through cwbl_reuse_info like the
+                                * record cache.  0 (default): nothing is kept and the path runs
+                                * as without the option; setting 0 releases what is held.
+                                * Accepted and ignored at k = 97..128 and on every other path
+                                * (k <= 64, CWBL_OPT_BIG_PATH = 0).  Group calls and
+                                * column-shared calls neither read, fill nor invalidate the
+                                * cache */
 };
 int         cwbl_set_option(int option, long long value);
 
