@@ -26,7 +26,7 @@
 // spills no registers (244 VGPRs, two waves per SIMD, 19.4 KB of LDS per wave).  Every loop
 // over steps, slots and columns is compile-time (sfor), so all register indices are static.
 //
-// What solve_tq40_multi_kernel (cwbl_tq40_multi.hip) runs as well is in cwbl_tq40_common.h:
+// What solve_tq40_multi_kernel (its body: cwbl_tq40_passes.h) runs as well is in cwbl_tq40_common.h:
 // the layout constants and the shared-memory struct, the row sums, dlarfg, the point decode,
 // the record load, the trace and the wave's quadrature rounds.  Phase 1, phase 2 and the
 // back-transform below are this kernel's own; the multi kernel has its b1-only twins.  The
@@ -407,7 +407,7 @@ solve_tq40_kernel(SolveConsts c, SlabDev slab, long long g0, int npts,
   // T^-1 u2.  Each row's sum over the round's 8 nodes is an 8-lane DPP reduction; its lane 0
   // hands it to the row's owner through LDS.
   // (Twin: the level loop, the round loop and d below are solve_tq40_multi_kernel's too, in
-  // cwbl_tq40_multi.hip: as shared functions they compile to other code)
+  // cwbl_tq40_passes.h: as shared functions they compile to other code)
   const double m = (double)c.inflat;
   const double ratio = trace / m - (double)(k - 1);
   int level = 1;

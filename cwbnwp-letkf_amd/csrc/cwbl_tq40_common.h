@@ -1,33 +1,33 @@
-// cwbl_tq40_common.h — what solve_tq40_kernel (cwbl_tq40.hip), solve_tq40_multi_kernel
-// (cwbl_tq40_multi.hip) and solve_tq40_column_kernel (cwbl_tq40_column.hip: the multi kernel's
-// text over the levels of a column) share: the layout (four points per wavefront, one 16-lane
-// DPP row per point; lane l holds the full rows J0 + l + 16 r of A in registers and, for
-// l < J0, row l of the top-left J0 x J0 prefix block), the row sums, the shared-memory struct, dlarfg, the point
-// decode, the record load, the trace and the wave's quadrature rounds.  Every function is
-// inlined into its kernel; the two kernels evaluate the same expressions in the same order, so
-// a variable's analysis is the same bit pattern from either.  The tridiagonalisations (and the
-// multi kernel's replay) are the kernels' own.  So are, as the same text in both files, the
-// quadrature's level and round loops and the RTPP/RTPS epilogue: each piece here was kept only
-// where both kernels compiled to the registers, LDS and instruction mix they had without it
-// and ran as fast.
+// cwbl_tq40_common.h — what solve_tq40_kernel (cwbl_tq40.hip) and tq40_passes
+// (cwbl_tq40_passes.h: the one body of solve_tq40_multi_kernel, over the variables of a group,
+// and of solve_tq40_column_kernel, over the levels of a column) share: the layout (four points
+// per wavefront, one 16-lane DPP row per point; lane l holds the full rows J0 + l + 16 r of A
+// in registers and, for l < J0, row l of the top-left J0 x J0 prefix block), the row sums, the
+// shared-memory struct, dlarfg, the point decode, the record load, the trace and the wave's
+// quadrature rounds.  Every function is inlined into its kernel; the kernels evaluate the
+// same expressions in the same order, so a variable's analysis is the same bit pattern from
+// any of them.  The tridiagonalisations (and the passes' replay) are the texts' own.  So are,
+// as the same text in both, the quadrature's level and round loops and the RTPP/RTPS
+// epilogue: each piece here was kept only where the kernels compiled to the registers, LDS
+// and instruction mix they had without it and ran as fast.
 //
-// The twin regions, for whoever changes the numerics (a fix lands in every file that has the
-// region; `single` = cwbl_tq40.hip, `multi` = cwbl_tq40_multi.hip, `column` =
-// cwbl_tq40_column.hip, whose text is multi's except for the loop head, the source of the
-// flags and the info store; `fill` and `factor` = fill_tq40_factor_kernel and
-// solve_tq40_factor_kernel in cwbl_tq40_fill.hip, which share one text, tq40_factor_solve, for
-// everything after the factor: multi's loop body at one variable, with Q^T b1, the accepted
-// count and the var index re-read or recomputed at their uses):
+// The twin regions, for whoever changes the numerics (a fix lands in every text that has the
+// region; `single` = cwbl_tq40.hip; `passes` = cwbl_tq40_passes.h, one text for the group and
+// the column kernel, which differ in its passes policy only; `fill` and `factor` =
+// fill_tq40_factor_kernel and solve_tq40_factor_kernel in cwbl_tq40_fill.hip, which share one
+// text, tq40_factor_solve, for everything after the factor: the passes' loop body at one
+// variable, with Q^T b1, the accepted count and the var index re-read or recomputed at their
+// uses):
 //   phase 1 and phase 2 of the tridiagonalisation   single (carries x' too, keeps x scal);
-//                                                   multi = column = fill (b1 only, keep x and
-//                                                   scal; fill stores them with beta and tau,
-//                                                   factor loads them: no step of its own)
-//   quadrature level loop and LDS walk offsets      single = multi = column = fill/factor
-//   replay of the reflectors on x'                  multi = column = fill/factor
-//   quadrature round loop and d                     single = multi = column = fill/factor
+//                                                   passes = fill (b1 only, keep x and scal;
+//                                                   fill stores them with beta and tau, factor
+//                                                   loads them: no step of its own)
+//   quadrature level loop and LDS walk offsets      single = passes = fill/factor
+//   replay of the reflectors on x'                  passes = fill/factor
+//   quadrature round loop and d                     single = passes = fill/factor
 //   back-transform                                  single (from x scal);
-//                                                   multi = column = fill/factor
-//   RTPP / RTPS epilogue and the store              single = multi = column = fill/factor
+//                                                   passes = fill/factor
+//   RTPP / RTPS epilogue and the store              single = passes = fill/factor
 #pragma once
 
 #include "cwbl_device.h"

@@ -14,30 +14,20 @@
 //                                    j >= J0 in the tail's — and then runs the quadrature, the
 //                                    back-transform and the epilogue both kernels share
 //                                    (tqb_finish).
-// cwbl_tq_tail.hip is left alone (its kernels' code must not move): what the pair shares with
-// solve_tqb_tail_kernel is repeated here.
-#include "cwbl_device.h"
+// Shared with solve_tqb_tail_kernel through cwbl_tq_tail_common.h: the shared-memory struct
+// (TailSmem), the point index and the fp32 readlane.  Both kept every kernel's instruction
+// stream as it was (profiles/twin_merge.txt).  The two larger texts are still repeated here,
+// because solve_tqb_tail_kernel, with either as a shared function, compiled to other vector
+// code than with its own text (the numbers are in cwbl_tq_tail_common.h): the fill's hand-off
+// load and Householder loop are the tail's with the factor's stores added, and tqb_finish is
+// the tail's quadrature, back-transform and epilogue as a function over two row loaders.
+#include "cwbl_tq_tail_common.h"
 
 #include <utility>
 
 namespace cwbl {
 
 namespace {
-
-__device__ __forceinline__ float bf_readlane_f32(float x, int l) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), l));
-}
-
-// TailSmem of cwbl_tq_tail.hip
-template <int KP, int J0>
-struct BigFactorSmem {
-  static constexpr int KT = KP - J0;
-  double row[KT];         // a row of the trailing 2x2 block's step (the fill)
-  double tq[KP + 1][4];   // d_i, c(i-1,i), (Q^T b1)_i, (Q^T x')_i
-  double tau[KP];
-  double scl[KP];         // the tail's reflectors: v = scl * x below row j + 1
-  double Ym[KP], Zm[KP];  // quadrature sum / exact solve, walk order
-};
 
 // var index of member 0 of point g
 __device__ __forceinline__ long long bf_point_index(const SlabDev &slab, long long g) {
@@ -55,7 +45,7 @@ __device__ __forceinline__ long long bf_point_index(const SlabDev &slab, long lo
 // (0 where !live), ld_hand(J, x0, x1) rows l and J0 + l of the hand-off kernel's reflector j
 // (x0 zero at rows <= j).
 template <int KP, int J0, class LdTail, class LdHand>
-__device__ __forceinline__ void tqb_finish(BigFactorSmem<KP, J0> &sm, const SolveConsts &c,
+__device__ __forceinline__ void tqb_finish(TailSmem<KP, J0> &sm, const SolveConsts &c,
                                            const SlabDev &slab, int gi, int l, int k, long long P,
                                            float xb0, float xb1, bool mem0, bool mem1,
                                            double trace, int ptot, int2 *__restrict__ info,
@@ -230,8 +220,8 @@ __device__ __forceinline__ void tqb_finish(BigFactorSmem<KP, J0> &sm, const Solv
   // sequential fp32 sum over members 0 .. k-1 (member m: slot m / J0, lane m % J0)
   auto seq_sum_f32 = [&](float a0, float a1) {
     float s = 0.0f;
-    for (int mm = 0; mm < J0; ++mm) s = s + bf_readlane_f32(a0, mm);
-    for (int mm = J0; mm < k; ++mm) s = s + bf_readlane_f32(a1, mm - J0);
+    for (int mm = 0; mm < J0; ++mm) s = s + readlane_f32(a0, mm);
+    for (int mm = J0; mm < k; ++mm) s = s + readlane_f32(a1, mm - J0);
     return s;
   };
   const double xb_mean = (double)(seq_sum_f32(xb0, xb1) * c.nmember_inv);  // fp32 (:671)
@@ -288,7 +278,7 @@ fill_tqb_tail_kernel(SolveConsts c, SlabDev slab, long long g0, int npts,
   constexpr int KT = HO::KT;  // trailing rows: one per lane
   constexpr int NG = KT / 8;  // column groups
   static_assert(KT == 64 && J0 <= 64 && J0 % 4 == 0, "one trailing row per lane; prefix rows on lanes < J0");
-  using SM = BigFactorSmem<KP, J0>;
+  using SM = TailSmem<KP, J0>;
   __shared__ SM sm;
 
   const int gi = xcd_remap_rev(blockIdx.x, gridDim.x);
@@ -511,7 +501,7 @@ solve_tqb_factor_kernel(SolveConsts c, SlabDev slab, long long g0, int npts,
   constexpr int NS = KT - 2;  // the tail's steps at k = KP
   static_assert(KT == 64 && KP > 64 && KP - 64 <= J0 && NS <= 2 * (J0 - 1),
                 "rows 64 .. KP-1 on the prefix lanes; two tail columns behind each head step");
-  using SM = BigFactorSmem<KP, J0>;
+  using SM = TailSmem<KP, J0>;
   __shared__ SM sm;
 
   const int gi = xcd_remap_rev(blockIdx.x, gridDim.x);  // the tail's XCD-chunk order
@@ -561,8 +551,8 @@ solve_tqb_factor_kernel(SolveConsts c, SlabDev slab, long long g0, int npts,
   // xb_mean = sum(xb) * nmember_inv in fp32 (:671), sequential like the reference (the hand-off
   // kernel sums the members in the same order)
   float xs = 0.0f;
-  for (int mm = 0; mm < J0; ++mm) xs = xs + bf_readlane_f32(xb0, mm);
-  for (int mm = J0; mm < k; ++mm) xs = xs + bf_readlane_f32(xb1, mm - J0);
+  for (int mm = 0; mm < J0; ++mm) xs = xs + readlane_f32(xb0, mm);
+  for (int mm = J0; mm < k; ++mm) xs = xs + readlane_f32(xb1, mm - J0);
   const double xb_mean = (double)(xs * c.nmember_inv);
   double ux0 = (double)xh0v - xb_mean;                 // x' of rows l (l < 64 < k)
   double ux1 = memh ? (double)xh1v - xb_mean : 0.0;    // x' of rows 64 + l, zeros past k

@@ -25,30 +25,14 @@
 // scratch rows, where the back-transform reads it.  Columns are processed in groups of
 // eight; the steps run in blocks by the group of column j + 1, so the groups left of it are
 // skipped at compile time and the rest run without selects.
-#include "cwbl_device.h"
+//
+// The shared-memory struct and the small helpers are cwbl_tq_tail_common.h's, which also
+// lists the regions of this text that the fill and the group kernel repeat, and why.
+#include "cwbl_tq_tail_common.h"
 
 #include <utility>
 
 namespace cwbl {
-
-namespace {
-
-
-__device__ __forceinline__ float readlane_f32(float x, int l) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), l));
-}
-
-}  // namespace
-
-template <int KP, int J0>
-struct TailSmem {
-  static constexpr int KT = KP - J0;
-  double row[KT];         // a row of the trailing 2x2 block's step
-  double tq[KP + 1][4];   // d_i, c(i-1,i), (Q^T b1)_i, (Q^T x')_i
-  double tau[KP];
-  double scl[KP];         // this kernel's reflectors: v = scl * x below row j + 1
-  double Ym[KP], Zm[KP];  // quadrature sum / exact solve, walk order
-};
 
 // WPE: waves per SIMD the register budget is sized for (2: 256 VGPRs, 3: 168)
 template <int KP, int J0, int WPE>

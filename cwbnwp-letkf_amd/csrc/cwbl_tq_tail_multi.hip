@@ -17,23 +17,16 @@
 // The back-transform streams the reflector rows from the record once per variable (the
 // L2/MALL serve the repeats of a point's rows within the loop).
 //
-// The body repeats cwbl_tq_tail.hip's text rather than sharing it, so that
-// solve_tqb_tail_kernel compiles to what it was.
-#include "cwbl_device.h"
+// The body repeats cwbl_tq_tail.hip's text rather than sharing it, so that both kernels
+// compile to what they were (cwbl_tq_tail_common.h, which holds the helpers
+// they do share, lists the regions and what sharing them changed).
+#include "cwbl_tq_tail_common.h"
 
 #include <utility>
 
 namespace cwbl {
 
-namespace {
-
-
-__device__ __forceinline__ float readlane_f32(float x, int l) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), l));
-}
-
-}  // namespace
-
+// TailSmem and the trailing Q^T x' of every variable
 template <int KP, int J0, int NV>
 struct TailMultiSmem {
   static constexpr int KT = KP - J0;
