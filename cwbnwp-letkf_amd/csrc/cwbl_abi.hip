@@ -254,6 +254,8 @@ struct KTime { long long launches = 0, points = 0; double ms = 0.0; };
 // point's BigFactor<96, 32> in the batch's region; a hit runs solve_tqb_factor_kernel on those and
 // nothing before it, one launch per sub-batch (CWBL_OPT_BIG_BATCH).  As with wave reuse one
 // record is one factor, inside the budget, and there is no FactorAux.
+// Rows reuse (CWBL_OPT_ROWS_REUSE): big reuse at KP = 128, behind the half-row hand-off kernel:
+// BigFactor<128, 64>, the same two kernels at <128, 64> (cwbl_tq_rows_factor.hip).
 struct RecordKey {
   unsigned long long gen;  // State::gen: obs set, cwbl_init constants, options
   int kp;                  // the path's KP (the record path: kTq4KP)
@@ -361,6 +363,7 @@ struct State {
   bool hit_merge = true;          // CWBL_OPT_HIT_MERGE: one hit launch per info window
   bool wave_reuse = false;        // CWBL_OPT_WAVE_REUSE: the factor cache of k = 41..64
   bool big_reuse = false;         // CWBL_OPT_BIG_REUSE: the factor cache of k = 65..96
+  bool rows_reuse = false;        // CWBL_OPT_ROWS_REUSE: the factor cache of k = 97..128
   bool host_pipe = false;         // CWBL_OPT_HOST_PIPE: group, column-shared and tune_q calls
                                   // pipe their host slabs per batch
   // the segment tables of a call's merged hit launches (HitSeg): written by the host, one
@@ -1123,9 +1126,12 @@ bool handoff_path() {
 // the one-wavefront path's calls that fill and read the factor cache (CWBL_OPT_WAVE_REUSE;
 // accepted and ignored at the smaller KP)
 bool wave_reuse_path() { return S.wave_reuse && wave_path() && S.kp > kTq4KP; }
-// the hand-off path's calls that fill and read the factor cache (CWBL_OPT_BIG_REUSE; accepted
-// and ignored at KP = 128 and on every other path)
-bool big_reuse_path() { return S.big_reuse && handoff_path() && S.kp == 96; }
+// the hand-off path's calls that fill and read the factor cache (CWBL_OPT_BIG_REUSE at KP = 96,
+// CWBL_OPT_ROWS_REUSE at KP = 128; each accepted and ignored at the other KP and on every other
+// path)
+bool big_reuse_path() {
+  return handoff_path() && (S.kp == 96 ? S.big_reuse : S.kp == kBigSplitKP && S.rows_reuse);
+}
 
 void make_record_key(RecordKey &key, const cwbl_var_params *vp, const cwbl_slab *sl) {
   std::memset(&key, 0, sizeof key);
@@ -1675,7 +1681,7 @@ long long sub_batch(int nb, long long cap) {
 // region's FactorAux entries (a cached batch under factor reuse; else null and unused).  On the
 // one-wavefront path crec is the batch's region of WaveFactors (CWBL_OPT_WAVE_REUSE): a fill
 // runs fill_tq_wave_kernel in solve_tq_kernel's place, a hit solve_tq_wave_factor_kernel.  On
-// the hand-off path it is the batch's region of BigFactors (CWBL_OPT_BIG_REUSE), every
+// the hand-off path it is the batch's region of BigFactors (CWBL_OPT_BIG_REUSE, CWBL_OPT_ROWS_REUSE), every
 // sub-batch's: a fill runs fill_tqb_tail_kernel in the tail's place, a hit
 // solve_tqb_factor_kernel alone.
 int solve_batch_path(VarCall &v, long long g0, int nb, const int *ncnt, const int *nidx,
@@ -2108,6 +2114,7 @@ int cwbl_init(const cwbl_init_params *p) {
   S.hit_merge = true;
   S.wave_reuse = false;
   S.big_reuse = false;
+  S.rows_reuse = false;
   S.host_pipe = false;
   S.ncu = prop.multiProcessorCount;
   std::memset(&P, 0, sizeof P);
@@ -2219,6 +2226,11 @@ int cwbl_set_option(int option, long long value) {
     case CWBL_OPT_BIG_REUSE:
       if (!range(0, 1)) break;
       S.big_reuse = value == 1;
+      if (S.cache.big) S.cache.release();  // off holds no memory
+      return CWBL_OK;
+    case CWBL_OPT_ROWS_REUSE:
+      if (!range(0, 1)) break;
+      S.rows_reuse = value == 1;
       if (S.cache.big) S.cache.release();  // off holds no memory
       return CWBL_OK;
     default:

@@ -486,14 +486,24 @@ struct BigFactor {
   static constexpr int WORDS = bt(KT - 2);
 };
 static_assert(BigFactor<96, 32>::WORDS <= 96 * 95 / 2 + 5 * 96, "the factor's bound");
-constexpr size_t big_factor_words(int kp) { return kp == 96 ? BigFactor<96, 32>::WORDS : 0; }
+// KP = 128 (CWBL_OPT_ROWS_REUSE, cwbl_tq_rows_factor.hip): the same struct over the half-row
+// hand-off kernel's 64 reflectors, 640 + 6112 + 1953 = 8705 words
+static_assert(BigFactor<128, 64>::WORDS <= 128 * 127 / 2 + 5 * 128, "the factor's bound");
+constexpr size_t big_factor_words(int kp) {
+  return kp == 96 ? BigFactor<96, 32>::WORDS : kp == 128 ? BigFactor<128, 64>::WORDS : 0;
+}
 // fill: launch_solve_tqb_tail on the hand-off kernel's records `ws`, which also leaves the npts
 // factors at `fac`; the hit: the same analysis from them and from info[i].x = p of the fill (no
-// lists, no trees, no hand-off kernel, no records).  KP = 96 only.
+// lists, no trees, no hand-off kernel, no records).  KP = 96 (cwbl_tq_big_factor.hip) and
+// KP = 128 (launch_*_rows, cwbl_tq_rows_factor.hip, which the two launchers pass on to).
 hipError_t launch_fill_tqb_tail(hipStream_t s, int kp, SolveConsts c, SlabDev slab, long long g0,
                                 int npts, double *ws, int2 *info, double *fac);
 hipError_t launch_solve_tqb_factor(hipStream_t s, int kp, SolveConsts c, SlabDev slab,
                                    long long g0, int npts, const double *fac, int2 *info);
+hipError_t launch_fill_tqb_tail_rows(hipStream_t s, SolveConsts c, SlabDev slab, long long g0,
+                                     int npts, double *ws, int2 *info, double *fac);
+hipError_t launch_solve_tqb_factor_rows(hipStream_t s, SolveConsts c, SlabDev slab, long long g0,
+                                        int npts, const double *fac, int2 *info);
 
 // KP = 96, 128: one 256-thread workgroup per point (cwbl_tq_big.hip)
 hipError_t launch_solve_tq_big(hipStream_t s, int kp, bool assembled, const TreeDesc *trees,

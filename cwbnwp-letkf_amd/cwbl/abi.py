@@ -30,7 +30,7 @@ OPT_SOLVER, OPT_SPLIT40, OPT_SPLIT40_BATCH, OPT_SEARCH = 1, 2, 3, 5
 OPT_BIG_PATH, OPT_BIG_BATCH, OPT_PAGEABLE, OPT_BIN_DIV, OPT_LEAD_DIV, OPT_MAX_BATCH = 6, 7, 8, 9, 10, 11
 OPT_INFO_WINDOW, OPT_INDEX, OPT_RECORD_REUSE = 12, 13, 14
 OPT_COLUMN_SHARE, OPT_COLUMN_LEVELS, OPT_FACTOR_REUSE, OPT_HIT_MERGE = 15, 16, 17, 18
-OPT_WAVE_REUSE, OPT_HOST_PIPE, OPT_BIG_REUSE = 19, 20, 21
+OPT_WAVE_REUSE, OPT_HOST_PIPE, OPT_BIG_REUSE, OPT_ROWS_REUSE = 19, 20, 21, 22
 OPTIONS = {"solver": OPT_SOLVER, "split40": OPT_SPLIT40, "split40_batch": OPT_SPLIT40_BATCH,
            "search": OPT_SEARCH,
            "big_path": OPT_BIG_PATH, "big_batch": OPT_BIG_BATCH, "pageable": OPT_PAGEABLE,
@@ -39,7 +39,8 @@ OPTIONS = {"solver": OPT_SOLVER, "split40": OPT_SPLIT40, "split40_batch": OPT_SP
            "record_reuse": OPT_RECORD_REUSE, "column_share": OPT_COLUMN_SHARE,
            "column_levels": OPT_COLUMN_LEVELS, "factor_reuse": OPT_FACTOR_REUSE,
            "hit_merge": OPT_HIT_MERGE, "wave_reuse": OPT_WAVE_REUSE,
-           "host_pipe": OPT_HOST_PIPE, "big_reuse": OPT_BIG_REUSE}
+           "host_pipe": OPT_HOST_PIPE, "big_reuse": OPT_BIG_REUSE,
+           "rows_reuse": OPT_ROWS_REUSE}
 
 #: cwbl_column_info_t.reason
 (COLUMN_SHARED, COLUMN_REASON_OFF, COLUMN_REASON_3D, COLUMN_REASON_Q1, COLUMN_REASON_NZ,

@@ -89,6 +89,9 @@ module letkf_core_gpu
     ! cwbl_set_option: calls of one variable at k = 65..96 keep each point's factor for the next
     ! call with the same localisation (1; 0, default: off), within CWBL_OPT_RECORD_REUSE's budget
     integer(c_int), parameter, public :: CWBL_OPT_BIG_REUSE = 21
+    ! cwbl_set_option: calls of one variable at k = 97..128 keep each point's factor for the next
+    ! call with the same localisation (1; 0, default: off), within CWBL_OPT_RECORD_REUSE's budget
+    integer(c_int), parameter, public :: CWBL_OPT_ROWS_REUSE = 22
     ! cwbl_set_option: host-memory slabs of group calls, column-shared calls and calls with
     ! tune_q = 1 travel batch by batch under the solves (1; 0, default: whole, around them)
     integer(c_int), parameter, public :: CWBL_OPT_HOST_PIPE = 20

@@ -432,7 +432,7 @@ enum {
                                 * option.  Bit-identical results and equal counters either
                                 * way.  Nothing that is cached depends on it: setting it leaves
                                 * a filled cache valid */
-  CWBL_OPT_BIG_REUSE = 21      /* 1: cwbl_analyze_var on the hand-off path at k = 65..96 (KP = 96,
+  CWBL_OPT_BIG_REUSE = 21,     /* 1: cwbl_analyze_var on the hand-off path at k = 65..96 (KP = 96,
                                 * default solver, CWBL_OPT_BIG_PATH = 1) keeps each point's
                                 * factor A = Q T Q^T for the next call, within the
                                 * CWBL_OPT_RECORD_REUSE budget (0 there turns this cache off
@@ -447,6 +447,23 @@ enum {
                                 * as without the option; setting 0 releases what is held.
                                 * Accepted and ignored at k = 97..128 and on every other path
                                 * (k <= 64, CWBL_OPT_BIG_PATH = 0).  Group calls and
+                                * column-shared calls neither read, fill nor invalidate the
+                                * cache */
+  CWBL_OPT_ROWS_REUSE = 22     /* 1: cwbl_analyze_var on the hand-off path at k = 97..128
+                                * (KP = 128, default solver, CWBL_OPT_BIG_PATH = 1) keeps each
+                                * point's factor A = Q T Q^T for the next call, as
+                                * CWBL_OPT_BIG_REUSE does at KP = 96 and within the same
+                                * CWBL_OPT_RECORD_REUSE budget (0 there turns this cache off
+                                * too): at most KP (KP - 1) / 2 + 5 KP fp64 words per point
+                                * (8705 words, 69.6 KB).  A later call with an equal key and
+                                * bit-equal coordinates runs no obs preparation, search,
+                                * assembly, hand-off kernel or tridiagonalisation: one
+                                * solve_tqb_factor_kernel per cached sub-batch
+                                * (CWBL_OPT_BIG_BATCH).  Bit-identical results and equal
+                                * counters; reported through cwbl_reuse_info.  0 (default):
+                                * nothing is kept and the path runs as without the option;
+                                * setting 0 releases what is held.  Accepted and ignored at
+                                * k <= 96 and under CWBL_OPT_BIG_PATH = 0.  Group calls and
                                 * column-shared calls neither read, fill nor invalidate the
                                 * cache */
 };

@@ -1,6 +1,7 @@
 #!/usr/bin/env python
-"""The factor cache of the hand-off path (CWBL_OPT_BIG_REUSE, k = 65..96), by the bench
-headline's procedure.
+"""The factor cache of the hand-off path (CWBL_OPT_BIG_REUSE at k = 65..96, CWBL_OPT_ROWS_REUSE
+at k = 97..128: the option is picked by the ensemble size's KP), by the bench headline's
+procedure.
 
 One run measures one library (CWBL_LIBRARY, or the tree's own).  Obs set and slab in device
 memory, `--warmup` untimed calls, then `--steps` calls timed as one block between two device
@@ -8,7 +9,7 @@ synchronisations (bench.py's timed region), through abi.Core.  Per mode
 
   off   the option absent: every call runs the QC columns, the search, the hand-off kernel and
         solve_tqb_tail_kernel
-  on    big_reuse = 1 and record_reuse = --budget MiB (the largest of --budget's values whose
+  on    the option = 1 and record_reuse = --budget MiB (the largest of --budget's values whose
         allocation succeeds): a miss runs the hand-off kernel and fill_tqb_tail_kernel, a hit
         solve_tqb_factor_kernel alone over the cached batches
 
@@ -21,7 +22,11 @@ by a warm call and (on) by the fill and the hit after it.  A library without the
 older build) is measured in the mode `off` alone.
 
   python scripts/big_reuse_ab.py [--config c2] [--k 96] [--budget MiB[,MiB...]] [--steps 3]
-                                 [--warmup 1] [--reps 2] [--scale S] [--no-hash]
+                                 [--warmup 1] [--reps 2] [--scale S] [--nz N] [--no-hash]
+
+--k 128, 112, 97 run configuration c4 unless --config names another; its whole grid's factors
+(313 GB) fit no single device, so --nz cuts the grid to its lowest N levels (--nz 25: 2.25 M
+points, 157 GB of factors).
 """
 import argparse
 import hashlib
@@ -36,15 +41,25 @@ sys.path.insert(0, os.path.join(REPO, "cwbnwp-letkf_amd"))
 
 from cwbl import abi, synth  # noqa: E402
 
-BIG_REUSE = 21  # by number: an older abi.py has no name for it
-FACTOR_BYTES = 8 * 4977  # BigFactor<96, 32>
+# by KP: the option (by number: an older abi.py has no name for it), the factor's bytes
+# (BigFactor<96, 32>, BigFactor<128, 64>) and the kernels' names
+BIG_REUSE, FACTOR_BYTES = 21, 8 * 4977
 HIT = "solve_tqb_factor_kernel<96, 32>"
 PAIR = ("solve_tq_big_kernel<96, false, 32>", "solve_tqb_tail_kernel<96, 32, 2>")
 FILL_PAIR = ("(fill) solve_tq_big_kernel<96, false, 32>", "(fill) fill_tqb_tail_kernel<96, 32>")
 
 
-def has_option():
-    c = abi.Core(96, device=0)
+def pick(k):
+    global BIG_REUSE, FACTOR_BYTES, HIT, PAIR, FILL_PAIR
+    if k > 96:
+        BIG_REUSE, FACTOR_BYTES = 22, 8 * 8705
+        HIT = "solve_tqb_factor_kernel<128, 64>"
+        PAIR = ("solve_tq_rows_kernel<128, 64>", "solve_tqb_tail_kernel<128, 64, 3>")
+        FILL_PAIR = ("(fill) solve_tq_rows_kernel<128, 64>", "(fill) fill_tqb_tail_kernel<128, 64>")
+
+
+def has_option(k):
+    c = abi.Core(k, device=0)
     try:
         c.set_option(BIG_REUSE, 1)
         return True
@@ -128,7 +143,7 @@ def spread(v):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", default="c2")
+    ap.add_argument("--config", default=None, help="c2 at k <= 96, c4 above")
     ap.add_argument("--k", type=int, default=96)
     ap.add_argument("--budget", default="200000,150000,100000,50000",
                     help="record_reuse in MiB: the first value whose cache allocation succeeds")
@@ -136,14 +151,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--scale", type=float, default=None, help="shrink the grid (trial runs)")
+    ap.add_argument("--nz", type=int, default=None, help="cut the grid to its lowest NZ levels")
     ap.add_argument("--no-hash", action="store_true")
     args = ap.parse_args()
-    w = synth.make(args.config, scale=args.scale, k=args.k)
+    pick(args.k)
+    args.config = args.config or ("c4" if args.k > 96 else "c2")
+    cut = {"nz": args.nz} if args.nz else {}
+    w = synth.make(args.config, scale=args.scale, k=args.k, **cut)
     print(f"== {args.config}: {w.nx}x{w.ny}x{w.nz} grid, k={w.k}, {w.obs.shape[0]} obs"
-          f"{' (scale %g)' % args.scale if args.scale else ''}; steps={args.steps} "
+          f"{' (scale %g)' % args.scale if args.scale else ''}"
+          f"{' (nz cut to %d)' % args.nz if args.nz else ''}; steps={args.steps} "
           f"warmup={args.warmup} reps={args.reps}; library "
           f"{os.environ.get('CWBL_LIBRARY', '(this tree)')}", flush=True)
-    modes = ("off", "on") if has_option() else ("off",)
+    modes = ("off", "on") if has_option(args.k) else ("off",)
     for mode in modes:
         r, budget = None, 0
         for budget in ([int(b) for b in args.budget.split(",")] if mode == "on" else [0]):
