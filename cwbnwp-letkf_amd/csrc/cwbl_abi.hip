@@ -232,30 +232,31 @@ enum KernelId {
 };
 struct KTime { long long launches = 0, points = 0; double ms = 0.0; };
 
-// Record reuse (CWBL_OPT_RECORD_REUSE): the k = 17..40 record path keeps what one call's
-// assemblies wrote, keyed by everything the record depends on.  The record holds A = inflat I
-// + Yb Yb^T and b1 = Yb d: functions of the obs set, the types' parameters, the weight
-// function, multi_infl and the point coordinates, not of the analysed variable (var enters in
-// solve_tq40_kernel only).  A later call with an equal key and bit-equal coordinates launches
-// the solves on the kept records and nothing before them.
-// Factor reuse (CWBL_OPT_FACTOR_REUSE, the default): the fill's solve, fill_tq40_factor_kernel,
-// leaves each cached point's factor A = Q T Q^T in its record's words (FactorRecord), and a hit
-// runs solve_tq40_factor_kernel on those, without the tridiagonalisation.  The steps' beta and
-// tau go to an entry of their own per cached record (FactorAux), outside the budget, which
-// bounds the records alone: what is cached does not depend on the form.  A cache holds one
-// form only: the option bumps the generation, which is part of the key.
-// Wave reuse (CWBL_OPT_WAVE_REUSE): the same cache on the one-wavefront path at KP = 48, 56, 64.
-// A fill's solve, fill_tq_wave_kernel, assembles and tridiagonalises as solve_tq_kernel does and
-// leaves each cached point's WaveFactor<KP> in the batch's region; a hit runs
-// solve_tq_wave_factor_kernel on those and nothing before it.  One record is one factor (`words`),
-// steps' scalars included: the budget bounds all of it, and there is no FactorAux.
-// Big reuse (CWBL_OPT_BIG_REUSE): the same cache on the hand-off path at KP = 96.  A fill runs the
-// hand-off kernel unchanged and fill_tqb_tail_kernel in the tail's place, which leaves each cached
-// point's BigFactor<96, 32> in the batch's region; a hit runs solve_tqb_factor_kernel on those and
-// nothing before it, one launch per sub-batch (CWBL_OPT_BIG_BATCH).  As with wave reuse one
-// record is one factor, inside the budget, and there is no FactorAux.
-// Rows reuse (CWBL_OPT_ROWS_REUSE): big reuse at KP = 128, behind the half-row hand-off kernel:
-// BigFactor<128, 64>, the same two kernels at <128, 64> (cwbl_tq_rows_factor.hip).
+// Record reuse (CWBL_OPT_RECORD_REUSE): a single-variable call keeps what its leading batches
+// computed before the analysed variable enters: functions of the obs set, the types' parameters,
+// the weight function, multi_infl and the point coordinates, which the key and a coordinate
+// snapshot cover.  A later call with an equal key and bit-equal coordinates (a hit) launches
+// the hit kernel on what was kept and nothing before it.  What is kept per point is the form:
+//   form        path (call_form)              a cached point      a fill's solve; a hit
+//   Records     k = 17..40, FACTOR_REUSE = 0  AsmRecord<40>       solve_tq40_kernel; the same
+//   Tq40Factor  k = 17..40, FACTOR_REUSE = 1  FactorRecord<40>    fill_tq40_factor_kernel;
+//                                             in its words        solve_tq40_factor_kernel
+//   WaveFactor  k = 41..64, WAVE_REUSE        WaveFactor<KP>      fill_tq_wave_kernel;
+//                                                                 solve_tq_wave_factor_kernel
+//   BigFactor   k = 65..96, BIG_REUSE         BigFactor<96, 32>   fill_tqb_tail_kernel behind the
+//               k = 97..128, ROWS_REUSE       BigFactor<128, 64>  hand-off kernel;
+//                                                                 solve_tqb_factor_kernel
+// The budget bounds the points' words.  Tq40Factor alone keeps more: beta and tau of the steps,
+// a FactorAux entry per record outside the budget, so what is cached does not depend on
+// FACTOR_REUSE.  The cached form and the live options cannot disagree on a hit: the key holds
+// State::gen and KP, and cwbl_set_option bumps gen for every option that call_form reads.
+enum class CacheForm { None, Records, Tq40Factor, WaveFactor, BigFactor };
+size_t form_words(CacheForm f, int kp) {  // fp64 words per cached point
+  return f == CacheForm::WaveFactor  ? wave_factor_words(kp)
+         : f == CacheForm::BigFactor ? big_factor_words(kp)
+                                     : (size_t)AsmRecord<kTq4KP>::WORDS;
+}
+bool form_has_aux(CacheForm f) { return f == CacheForm::Tq40Factor; }  // a FactorAux per point
 struct RecordKey {
   unsigned long long gen;  // State::gen: obs set, cwbl_init constants, options
   int kp;                  // the path's KP (the record path: kTq4KP)
@@ -275,10 +276,8 @@ struct RecordCache {
   // ordinal: batch b's entries start at entry off[b] / WORDS, sub-batch s0's s0 entries on.
   DevBuf rec, aux, info, sx, sy, salt, flag;
   PinBuf hflag;
-  size_t words = AsmRecord<kTq4KP>::WORDS;  // fp64 words of a record: AsmRecord, WaveFactor or
-                                             // BigFactor
-  bool wave = false;                         // the allocation last served the one-wavefront path
-  bool big = false;                          // ... the hand-off path
+  CacheForm form = CacheForm::None;  // what the allocation last served (begin_fill)
+  size_t words() const { return form_words(form, key.kp); }  // fp64 words of a record
   std::vector<std::pair<long long, int>> plan;
   std::vector<size_t> off;
   long long pts = 0;
@@ -289,8 +288,7 @@ struct RecordCache {
   size_t bytes() const { return rec.n + aux.n + info.n + sx.n + sy.n + salt.n + flag.n; }
   void release() {
     valid = false;
-    wave = false;
-    big = false;
+    form = CacheForm::None;
     for (DevBuf *b : {&rec, &aux, &info, &sx, &sy, &salt, &flag}) b->release();
     hflag.release();
     plan.clear();
@@ -1132,6 +1130,13 @@ bool wave_reuse_path() { return S.wave_reuse && wave_path() && S.kp > kTq4KP; }
 bool big_reuse_path() {
   return handoff_path() && (S.kp == 96 ? S.big_reuse : S.kp == kBigSplitKP && S.rows_reuse);
 }
+// the form that a single-variable call on the current path and options fills and reads
+CacheForm call_form() {
+  if (record_path()) return S.factor_reuse ? CacheForm::Tq40Factor : CacheForm::Records;
+  if (wave_reuse_path()) return CacheForm::WaveFactor;
+  if (big_reuse_path()) return CacheForm::BigFactor;
+  return CacheForm::None;
+}
 
 void make_record_key(RecordKey &key, const cwbl_var_params *vp, const cwbl_slab *sl) {
   std::memset(&key, 0, sizeof key);
@@ -1167,22 +1172,18 @@ int coords_match(VarCall &v, bool &same) {
 // records fit the budget, allocates what they need (kept from an earlier fill when it is
 // large enough) and takes the coordinate snapshot.  The batches then assemble into their own
 // regions instead of S.wsa.  A failed allocation is no error: the call runs without reuse.
-int begin_fill(VarCall &v, const RecordKey &key) {
+int begin_fill(VarCall &v, const RecordKey &key, CacheForm form) {
   RecordCache &C = S.cache;
   C.valid = false;
   C.key = key;
   C.plan = v.plan;
   C.off.clear();
   C.pts = 0;
-  C.wave = wave_reuse_path();
-  C.big = big_reuse_path();
-  C.words = C.wave  ? wave_factor_words(S.kp)
-            : C.big ? big_factor_words(S.kp)
-                    : (size_t)AsmRecord<kTq4KP>::WORDS;
+  C.form = form;
   size_t words = 0;
   for (const auto &b : v.plan) {
     // (+1: the spare record; the wave kernels read none, the region's layout is one)
-    const size_t need = ((size_t)b.second + 1) * C.words;
+    const size_t need = ((size_t)b.second + 1) * C.words();
     if ((words + need) * sizeof(double) > S.reuse_budget) break;
     C.off.push_back(words);
     words += need;
@@ -1200,7 +1201,7 @@ int begin_fill(VarCall &v, const RecordKey &key) {
             C.rec.ensure(std::min(S.reuse_budget, need + need / 16)) == hipSuccess;
   // The steps' scalars of the factors, an entry per record: beside the budget's cut, like info
   // and the snapshot, with the same headroom; a cache of records holds none
-  if (S.factor_reuse && !C.wave && !C.big) {
+  if (form_has_aux(form)) {
     const size_t aneed =
         words / AsmRecord<kTq4KP>::WORDS * FactorAux<kTq4KP>::WORDS * sizeof(double);
     ok = ok && (aneed <= C.aux.n || C.aux.ensure(aneed + aneed / 16) == hipSuccess);
@@ -1665,6 +1666,12 @@ long long sub_batch(int nb, long long cap) {
   const long long Bs = (nb + nsub - 1) / nsub;
   return std::max<long long>(kListLanes, (Bs + kListLanes - 1) / kListLanes * kListLanes);
 }
+// The record path's sub-batch: CWBL_OPT_SPLIT40_BATCH, and at most 2^19 points (the solve
+// addresses a sub-batch's records with 32-bit byte offsets).  A merged hit's segments are these.
+long long record_sub_batch(int nb) {
+  const long long cap = std::min<long long>(S.tq4_sub > 0 ? S.tq4_sub : nb, 1 << 19);
+  return std::min<long long>(sub_batch(nb, cap), 1 << 19);
+}
 
 // letkf_yoyb + letkf_solve (module_letkf_core.f90:300-700) for batch (g0, nb) on S.stream, one
 // path per ensemble-size class:
@@ -1676,17 +1683,15 @@ long long sub_batch(int nb, long long cap) {
 //   otherwise    one wavefront per point: solve_tq_kernel, or solve_tq_multi_kernel for a
 //                group call; CWBL_OPT_SOLVER = 1: the Jacobi eigensolver kernel (k <= 64)
 // b2 / dn: the events around the batch's solve (the record path times its kernel pair
-// between them).  crec (record path): the batch's region of the record cache, which a fill
-// assembles into and a hit (no lists, no assembly) solves from; null: S.wsa.  caux: that
-// region's FactorAux entries (a cached batch under factor reuse; else null and unused).  On the
-// one-wavefront path crec is the batch's region of WaveFactors (CWBL_OPT_WAVE_REUSE): a fill
-// runs fill_tq_wave_kernel in solve_tq_kernel's place, a hit solve_tq_wave_factor_kernel.  On
-// the hand-off path it is the batch's region of BigFactors (CWBL_OPT_BIG_REUSE, CWBL_OPT_ROWS_REUSE), every
-// sub-batch's: a fill runs fill_tqb_tail_kernel in the tail's place, a hit
-// solve_tqb_factor_kernel alone.
+// between them).  crec: a cached batch's region of the record cache (every sub-batch's), in
+// the call's form (the table above RecordKey; None with a null crec), which a fill (hit false)
+// writes and a hit (no lists, no trees) solves from.  Record path: a fill assembles into crec
+// in S.wsa's place; caux is the region's FactorAux entries (Tq40Factor; else null and unused).
+// One-wavefront path: a fill runs fill_tq_wave_kernel in solve_tq_kernel's place.  Hand-off
+// path: a fill runs fill_tqb_tail_kernel in the tail's place, a hit no hand-off kernel.
 int solve_batch_path(VarCall &v, long long g0, int nb, const int *ncnt, const int *nidx,
                      int2 *infob, hipEvent_t b2, hipEvent_t dn, double *crec = nullptr,
-                     bool hit = false, double *caux = nullptr) {
+                     CacheForm form = CacheForm::None, bool hit = false, double *caux = nullptr) {
   const TreeDesc *dtrees = S.tdesc.as<TreeDesc>();
   const SolveConsts &c = v.c;
   const SlabDev &sd = v.sd;
@@ -1694,19 +1699,16 @@ int solve_batch_path(VarCall &v, long long g0, int nb, const int *ncnt, const in
   int kt;
   const bool handoff = handoff_path();
   if (record_path()) {
-    // (Bs <= 2^19: the solve addresses a sub-batch's records with 32-bit byte offsets)
-    const long long cap = std::min<long long>(S.tq4_sub > 0 ? S.tq4_sub : nb, 1 << 19);
-    const long long Bs = std::min<long long>(sub_batch(nb, cap), 1 << 19);
+    const long long Bs = record_sub_batch(nb);
     // (+1: the spare record of solve_tq40_kernel's lanes past the sub-batch)
     if (!crec) HIPCHK(S.wsa.ensure((size_t)(Bs + 1) * 8 * AsmRecord<kTq4KP>::WORDS));
     double *rec = crec ? crec : S.wsa.as<double>();
     // a cached batch keeps every sub-batch's records, S.wsa only the current one's
     const size_t rstep = crec ? AsmRecord<kTq4KP>::WORDS : 0;
     // the solve of n points from g: one variable's, or the group's over all its variables
-    // A cached batch under CWBL_OPT_FACTOR_REUSE keeps factors: its fill solves with
-    // fill_tq40_factor_kernel, which leaves the factor over each record, and a hit with
-    // solve_tq40_factor_kernel.  (A group call never has a cached batch.)
-    const bool factor = crec && S.factor_reuse && !v.group;
+    // A cached batch of factors: its fill's solve leaves the factor over each record.  (A group
+    // call never has a cached batch.)
+    const bool factor = form == CacheForm::Tq40Factor;
     const int kt_solve = factor ? (hit ? KT_SOLVE_TQ40_FACTOR : KT_FILL_TQ40_FACTOR)
                          : v.group ? KT_SOLVE_TQ40_MULTI : KT_SOLVE_TQ40;
     auto solve = [&](long long g, int n, double *r, int2 *inf) {
@@ -1761,7 +1763,7 @@ int solve_batch_path(VarCall &v, long long g0, int nb, const int *ncnt, const in
         kListLanes, (long long)(S.handoff_budget / rec_bytes) / kListLanes * kListLanes);
     const long long Bs = sub_batch(nb, std::min<long long>(S.big_sub, fit));
     // a cached batch of the factor cache: sub-batch s0 starts s0 factors into its region
-    const bool bigf = crec && !v.group;
+    const bool bigf = form == CacheForm::BigFactor;
     const size_t fwords = big_factor_words(S.kp);
     if (!(bigf && hit)) HIPCHK(S.wsa.ensure((size_t)Bs * rec_bytes));
     for (long long s0 = 0; s0 < nb; s0 += Bs) {
@@ -1814,7 +1816,7 @@ int solve_batch_path(VarCall &v, long long g0, int nb, const int *ncnt, const in
     HIPCHK(kt_end(S.stream, kt, nv == 2 ? KT_SOLVE_TQ_MULTI2 : nv == 4 ? KT_SOLVE_TQ_MULTI4
                                                                       : KT_SOLVE_TQ_MULTI8,
                   (long long)nb * v.lev));
-  } else if (crec) {  // a cached batch of the factor cache (CWBL_OPT_WAVE_REUSE)
+  } else if (form == CacheForm::WaveFactor) {  // a cached batch (CWBL_OPT_WAVE_REUSE)
     if (hit) {
       HIPCHK(launch_solve_tq_wave_factor(S.stream, S.kp, c, sd, g0, nb, crec, infob));
     } else {
@@ -1918,8 +1920,7 @@ int solve_batch_column(VarCall &v, long long g0, int nb, const int *ncnt, const 
     return CWBL_OK;
   }
   const TreeDesc *dtrees = S.tdesc.as<TreeDesc>();
-  const long long cap = std::min<long long>(S.tq4_sub > 0 ? S.tq4_sub : nb, 1 << 19);
-  const long long Bs = std::min<long long>(sub_batch(nb, cap), 1 << 19);
+  const long long Bs = record_sub_batch(nb);
   HIPCHK(S.wsa.ensure((size_t)(Bs + 1) * 8 * AsmRecord<kTq4KP>::WORDS));
   double *const rec = S.wsa.as<double>();
   int kt;
@@ -2221,17 +2222,17 @@ int cwbl_set_option(int option, long long value) {
     case CWBL_OPT_WAVE_REUSE:
       if (!range(0, 1)) break;
       S.wave_reuse = value == 1;
-      if (S.cache.wave) S.cache.release();  // off holds no memory (a record cache keeps its own)
+      if (S.cache.form == CacheForm::WaveFactor) S.cache.release();  // off holds no memory
       return CWBL_OK;
     case CWBL_OPT_BIG_REUSE:
       if (!range(0, 1)) break;
       S.big_reuse = value == 1;
-      if (S.cache.big) S.cache.release();  // off holds no memory
+      if (S.cache.form == CacheForm::BigFactor) S.cache.release();  // off holds no memory
       return CWBL_OK;
     case CWBL_OPT_ROWS_REUSE:
       if (!range(0, 1)) break;
       S.rows_reuse = value == 1;
-      if (S.cache.big) S.cache.release();  // off holds no memory
+      if (S.cache.form == CacheForm::BigFactor) S.cache.release();  // off holds no memory
       return CWBL_OK;
     default:
       return fail(CWBL_ERR_ARG, "cwbl_set_option: unknown option %d", option);
@@ -2404,16 +2405,15 @@ static int begin_call(const cwbl_slab *sl) {
 // with its events (profiles/hit_merge.txt).  The segments of a cached batch are what
 // solve_batch_path launches for it: the batch, or its sub-batches under CWBL_OPT_SPLIT40_BATCH.
 static long long hit_segments(int nb, long long *Bs_out = nullptr) {
-  const long long cap = std::min<long long>(S.tq4_sub > 0 ? S.tq4_sub : nb, 1 << 19);
-  const long long Bs = std::min<long long>(sub_batch(nb, cap), 1 << 19);
+  const long long Bs = record_sub_batch(nb);
   if (Bs_out) *Bs_out = Bs;
   return Bs >= nb ? 1 : (nb + Bs - 1) / Bs;
 }
 
 // Whether the call's cached batches go out merged, and room for their segment tables.
-static int plan_hit_merge(VarCall &v) {
-  // (the record path's: a hit of the one-wavefront path's cache is one launch per batch)
-  v.merge = S.hit_merge && record_path() && v.reuse == 2 && S.factor_reuse && !v.group &&
+static int plan_hit_merge(VarCall &v, CacheForm form) {
+  // (the other factor forms' hits are one launch per batch or sub-batch)
+  v.merge = S.hit_merge && form == CacheForm::Tq40Factor && v.reuse == 2 && !v.group &&
             !v.colshare && !v.piped && !v.piped_back && !v.bounce && v.ncached > 0;
   if (!v.merge) return CWBL_OK;
   long long nseg = 0;
@@ -2506,9 +2506,9 @@ static int analyze_call(VarCall &v, cwbl_stats *stats) {
   // call does; the planned trees confirm it below.
   CI.reason = column_reason(v);
   const bool col_candidate = CI.reason == CWBL_COLUMN_SHARED;
+  const CacheForm form = call_form();
   const bool reuse_on =
-      !v.group && !col_candidate && (record_path() || wave_reuse_path() || big_reuse_path()) &&
-      S.reuse_budget > 0 && npts > 0;
+      !v.group && !col_candidate && form != CacheForm::None && S.reuse_budget > 0 && npts > 0;
   RecordKey key;
   bool staged = false;
   if (reuse_on) {
@@ -2572,8 +2572,8 @@ static int analyze_call(VarCall &v, cwbl_stats *stats) {
   if (int rc = stage_bounce(v)) return rc;
   if (int rc = alloc_call_buffers(v)) return rc;
   if (reuse_on && v.reuse != 2)
-    if (int rc = begin_fill(v, key)) return rc;
-  if (int rc = plan_hit_merge(v)) return rc;
+    if (int rc = begin_fill(v, key, form)) return rc;
+  if (int rc = plan_hit_merge(v, form)) return rc;
   if (int rc = restore_info(v, 0)) return rc;
   HIPCHK(event(3, &e_ready));  // inputs staged and the counters cleared
   HIPCHK(hipEventRecord(e_ready, S.stream));
@@ -2609,9 +2609,8 @@ static int analyze_call(VarCall &v, cwbl_stats *stats) {
     HIPCHK(event(ev + 3, &dn));
     // a cached batch: its region of the record cache; on a hit neither lists nor assembly
     double *const crec = bi < v.ncached ? C.rec.as<double>() + C.off[bi] : nullptr;
-    const size_t aoff = crec ? C.off[bi] / C.words * FactorAux<kTq4KP>::WORDS : 0;
-    double *const caux =
-        crec && S.factor_reuse && !C.wave && !C.big ? C.aux.as<double>() + aoff : nullptr;
+    const size_t aoff = crec ? C.off[bi] / C.words() * FactorAux<kTq4KP>::WORDS : 0;
+    double *const caux = crec && form_has_aux(form) ? C.aux.as<double>() + aoff : nullptr;
     const bool hit = crec && v.reuse == 2;
     if (hit && v.merge) {
       // the cached batches of this window: [bi, be)
@@ -2645,8 +2644,8 @@ static int analyze_call(VarCall &v, cwbl_stats *stats) {
     HIPCHK(hipEventRecord(b2, S.stream));
     if (v.colshare) {
       if (int rc = solve_batch_column(v, g0, nb, ncnt, nidx, infob, b2, dn)) return rc;
-    } else if (int rc = solve_batch_path(v, g0, nb, ncnt, nidx, infob, b2, dn, crec, hit,
-                                       caux)) {
+    } else if (int rc = solve_batch_path(v, g0, nb, ncnt, nidx, infob, b2, dn, crec,
+                                       crec ? form : CacheForm::None, hit, caux)) {
       return rc;
     }
     HIPCHK(hipEventRecord(dn, S.stream));  // this batch's lists are free again

@@ -19,7 +19,7 @@ import pytest
 from cwbl import abi, synth
 
 import spectra_cases as sc
-from test_gpu_record_reuse import (Inputs, Run, bits, is_hit, is_miss, no_reuse, other_var, same)
+from reuse_harness import (Inputs, Run, bits, is_hit, is_miss, no_reuse, other_var, same)
 
 pytestmark = pytest.mark.gpu
 

@@ -16,7 +16,7 @@ import pytest
 
 from cwbl import abi, synth
 
-from test_gpu_record_reuse import Inputs, Run, is_hit, is_miss, no_reuse, other_var, same
+from reuse_harness import Inputs, Run, is_hit, is_miss, no_reuse, other_var, same
 
 pytestmark = pytest.mark.gpu
 

@@ -23,8 +23,8 @@ import spectra_cases as sc
 from cwbl import synth
 from helpers import inflat_of, quad_level, radar_point_columns, spectrum_ratio
 
+from reuse_harness import Inputs, Run, bits, is_hit, is_miss, no_reuse, other_var
 from test_gpu_hit_merge import hit_launches
-from test_gpu_record_reuse import Inputs, Run, bits, is_hit, is_miss, no_reuse, other_var
 
 pytestmark = pytest.mark.gpu
 

@@ -9,141 +9,22 @@ takes for hits were hits and the ones it takes for misses were misses.
 Workload: synth c2 at scale 0.1 (30 x 30 x 50 points, k = 40, 225 obs) in search batches of
 1024 points and record sub-batches of 512, i.e. 44 batches of two sub-batches each.
 """
-import copy
-
 import numpy as np
 import pytest
 
 from cwbl import abi, synth
+from reuse_harness import Inputs, Run, bits, is_hit, is_miss, no_reuse, other_var, same
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-OPTS = {"max_batch": 1024, "split40_batch": 512}
-COUNTERS = ("points", "solved", "nobs_sum", "lz_truncated", "nonconverged", "q1_undefined",
-            "sweeps_sum", "max_p", "max_sweeps", "ntrees")
 REC_BYTES = 6880  # AsmRecord<40>: 860 fp64 words
-
-
-def counters(st):
-    return {n: getattr(st, n) for n in COUNTERS}
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def to_dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).to("cuda:0")
 
 
 @pytest.fixture(scope="module")
 def w():
     return synth.make("c2", scale=0.1)
-
-
-def other_var(w, seed):
-    """Another variable on the same grid: the same shape, other values."""
-    rng = np.random.default_rng(seed)
-    return (w.var + rng.standard_normal(w.var.shape, dtype=np.float32)).astype(np.float32)
-
-
-class Inputs:
-    """Everything a call depends on but var; copied so that a test can change any of it."""
-
-    def __init__(self, w):
-        self.k, self.radar_type = w.k, w.radar_type
-        self.x, self.y, self.alt = w.x.copy(), w.y.copy(), w.alt.copy()
-        self.obs_xyz, self.obs, self.hdxb = w.obs_xyz, w.obs, w.hdxb
-        self.vp = copy.deepcopy(w.vp)
-        self.ix_lim = None
-        self.options = {}
-
-    @property
-    def tp(self):
-        return self.vp.radar[self.radar_type - 1]
-
-
-class Run:
-    """One library state: the slab's coordinates live in device buffers that stay where they
-    are (sync() rewrites them in place), var is uploaded afresh for every call."""
-
-    def __init__(self, inp, reuse=None, opts=None, host=False):
-        options = dict(OPTS)
-        options.update(opts or {})
-        if reuse is not None:
-            options["record_reuse"] = reuse
-        self.c = abi.Core(inp.k, device=0, options=options)
-        self.host = host
-        self.inp = inp
-        self.x, self.y, self.alt = (a.copy() if host else to_dev(a) for a in (inp.x, inp.y, inp.alt))
-        self.hdxb = None
-        self.applied = {}
-        self.sync(inp)
-
-    def sync(self, inp):
-        self.inp = inp
-        for dst, src in ((self.x, inp.x), (self.y, inp.y), (self.alt, inp.alt)):
-            if self.host:
-                dst[...] = src
-            else:
-                dst.copy_(torch.from_numpy(src))
-        if inp.hdxb is not self.hdxb:
-            self.c.set_obs(abi.ObsSetBuilder().add_radar(inp.radar_type, inp.obs_xyz, inp.obs,
-                                                         inp.hdxb).build())
-            self.hdxb = inp.hdxb
-        for name, value in inp.options.items():
-            if self.applied.get(name) != value:
-                self.c.set_option(name, value)
-                self.applied[name] = value
-
-    def call(self, var):
-        """Analyse a copy of `var`: (analysis, counters, reuse_info)."""
-        inp = self.inp
-        if self.host:
-            v = np.array(var, np.float32, copy=True)
-            slab = abi.make_slab(self.x, self.y, self.alt, v, ix_lim=inp.ix_lim)
-        else:
-            v = to_dev(var)
-            torch.cuda.synchronize()
-            slab = abi.make_slab(self.x, self.y, self.alt, v, ix_lim=inp.ix_lim,
-                                 memory=abi.MEM_DEVICE)
-        st = self.c.analyze_var(inp.vp, slab)
-        out = v if self.host else v.cpu().numpy()
-        return out, counters(st), self.c.reuse_info().as_dict()
-
-    def close(self):
-        self.c.finalize()
-
-
-def no_reuse(inp, variables, opts=None):
-    """The analyses of `variables` with record_reuse = 0, one after the other."""
-    r = Run(inp, reuse=0, opts=opts)
-    try:
-        outs = []
-        for var in variables:
-            out, cnt, info = r.call(var)
-            assert info["batches_reused"] == 0 and info["bytes_held"] == 0, info
-            outs.append((out, cnt))
-        return outs
-    finally:
-        r.close()
-
-
-def is_miss(info, nbat=None):
-    assert info["batches_reused"] == 0 and info["batches_assembled"] > 1, info
-    assert nbat is None or info["batches_assembled"] == nbat, info
-
-
-def is_hit(info, nbat):
-    assert info["batches_reused"] == nbat and info["batches_assembled"] == 0, info
-    assert info["bytes_held"] > 0, info
-
-
-def same(got, want):
-    assert got[1] == want[1], (got[1], want[1])
-    assert np.array_equal(bits(got[0]), bits(want[0]))
 
 
 def test_hit_equals_no_reuse(w):
