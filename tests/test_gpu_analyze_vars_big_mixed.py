@@ -4,7 +4,9 @@ localisation: two normalisations, two searches), Gaspari-Cohn weighting with its
 (Q8), and truncated neighbour lists (max_lz_pts below the largest p: the k-d tree re-search,
 inside the group call's shared search).  The golden driver cases stop at k = 40, so
 solve_tq_big_kernel / solve_tq_rows_kernel / solve_tqb_tail_kernel and their group forms see
-these inputs only here.
+these radar inputs only here.  Both types have nvar = 1: GTS types with several variables per
+obs (and 2-D trees, the Q1 rules, is_assim, QC flags and per-variable err_muti / err_rej) at
+k = 41..128 are in tests/test_gpu_gts_large_k.py.
 
 Per case: cwbl_analyze_var against the oracle at INCR_TOL with NaNs at identical positions and
 equal solved / nobs_sum / lz_truncated; cwbl_analyze_vars (three variables) against the
