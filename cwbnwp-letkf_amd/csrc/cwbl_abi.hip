@@ -227,7 +227,7 @@ enum KernelId {
   KT_BIG_HANDOFF, KT_TQB_TAIL, KT_FILL_TQB_TAIL, KT_SOLVE_TQB_FACTOR, KT_BIG_HANDOFF_MULTI2, KT_BIG_HANDOFF_MULTI4,
   KT_BIG_HANDOFF_MULTI8, KT_TQB_TAIL_MULTI2, KT_TQB_TAIL_MULTI4, KT_TQB_TAIL_MULTI8,
   KT_SOLVE_TQ, KT_FILL_TQ_WAVE, KT_SOLVE_TQ_WAVE_FACTOR, KT_SOLVE_TQ_BIG, KT_SOLVE_JACOBI,
-  KT_TUNE_Q,
+  KT_TUNE_Q, KT_SOLVE_TQ_WAVE_FACTOR_COLUMN, KT_SOLVE_TQB_FACTOR_COLUMN,
   KT_COUNT
 };
 struct KTime { long long launches = 0, points = 0; double ms = 0.0; };
@@ -328,6 +328,7 @@ struct State {
   DevBuf qxyz, qnf, qidx, qr2;                        // search staging
   DevBuf quad;                                        // x^-1/2 quadrature tables
   DevBuf wsa;                                         // hand-off records (split KP=40 path)
+  DevBuf wsf;  // CWBL_OPT_COLUMN_FACTOR: the factors of a (sub-)batch's columns, for the call
   DevBuf flags;                                       // binned search: flagged points (+ count)
   int index_mode = 0;                                 // CWBL_OPT_INDEX
   DevBuf tdesc_tree;                                  // index mode 1: the tree searches' table
@@ -370,6 +371,8 @@ struct State {
   PinBuf hitseg_pin;
   int column_share = 0;           // CWBL_OPT_COLUMN_SHARE: 0 off, 1 column kernel, 2 chunks only
   int column_levels = 0;          // CWBL_OPT_COLUMN_LEVELS: levels per wave (0: automatic)
+  bool column_factor = false;     // CWBL_OPT_COLUMN_FACTOR: a shared call's levels from one kept
+                                  // factor per column (k = 41..96)
   int ncu = 0;                    // compute units of the device (automatic level split)
   RecordCache cache;
   // pageable host slabs: each batch's var columns go through page-locked bounce slots (two
@@ -556,6 +559,10 @@ std::string kernel_name(int id) {
     case KT_SOLVE_TQ_BIG: return "solve_tq_big_kernel<" + kp + ", false>";
     case KT_SOLVE_JACOBI: return "solve_kernel<" + kp + ", false>";
     case KT_TUNE_Q: return "tune_q_kernel";
+    case KT_SOLVE_TQ_WAVE_FACTOR_COLUMN: return "solve_tq_wave_factor_column_kernel<" + kp + ">";
+    case KT_SOLVE_TQB_FACTOR_COLUMN:
+      return "solve_tqb_factor_column_kernel<" + kp + ", " + std::to_string(big_split_j0(S.kp)) +
+             ">";
   }
   return "?";
 }
@@ -971,7 +978,7 @@ void release_all() {
   S.cevents.clear();
   for (DevBuf *b : {&S.tdesc, &S.nbr_cnt, &S.nbr_idx, &S.nbr_cnt2, &S.nbr_idx2, &S.info, &S.stats, &S.sx,
                     &S.sy, &S.salt, &S.svar, &S.bcol, &S.byo, &S.byb, &S.bxb, &S.bxa, &S.bev, &S.btri,
-                    &S.qxyz, &S.qnf, &S.qidx, &S.qr2, &S.quad, &S.wsa, &S.flags, &S.tdesc_tree,
+                    &S.qxyz, &S.qnf, &S.qidx, &S.qr2, &S.quad, &S.wsa, &S.wsf, &S.flags, &S.tdesc_tree,
                     &S.ix_keys[0], &S.ix_keys[1], &S.ix_vals[0], &S.ix_vals[1], &S.ix_hist,
                     &S.ix_part, &S.hitseg})
     b->release();
@@ -1867,10 +1874,105 @@ int column_levels_per_wave(int ncol, int nz) {
   return std::max(lw, (nz + 65534) / 65535);  // gridDim.y
 }
 
+// CWBL_OPT_COLUMN_FACTOR: a shared call's levels from one kept factor per column, where the
+// path has a factor form with a fill and a hit kernel and the level kernel met its bar
+// (DESIGN.md §3.6): the one-wavefront path at KP = 48, 56, 64 and the hand-off path at KP = 96.
+// Accepted and ignored elsewhere (k <= 40, k = 97..128).
+bool column_factor_path() {
+  return S.column_factor && ((wave_path() && S.kp > kTq4KP) || (handoff_path() && S.kp == 96));
+}
+
+// Levels per wavefront of a level kernel's launch over ncol columns and the nl = nz - 1 levels
+// above level 0, one column per wavefront: the option, or all nl unless the columns are fewer
+// than twice the wavefronts the device holds of the kernel (TqOccupancy per SIMD); then the
+// fewest level ranges that reach that many.
+int factor_levels_per_wave(int ncol, int nl) {
+  int lw = nl;
+  if (S.column_levels > 0) {
+    lw = std::min(S.column_levels, nl);
+  } else {
+    const long long want = 2LL * S.ncu * 4 * (S.kp == 48 ? 3 : 2);
+    if (ncol < want) {
+      const long long ranges = std::min<long long>(nl, (want + ncol - 1) / ncol);
+      lw = (int)((nl + ranges - 1) / ranges);
+    }
+  }
+  return std::max(lw, (nl + 65534) / 65535);  // gridDim.y
+}
+
+// The solves of batch (g0, nb) of a column-shared call under CWBL_OPT_COLUMN_FACTOR (v.sd is the
+// column view, v.full the slab).  Per (sub-)batch of ns columns: the factor cache's fill on the
+// column view analyses level 0 as the single kernels do and leaves the ns factors in S.wsf, a
+// workspace of the call; one launch of the level kernel then solves the levels 1 .. nz-1 of
+// every column from them.  The record cache is not involved.  done = false (and nothing
+// launched) when the workspace cannot be allocated: the caller runs the chunks, no error.
+int solve_batch_column_factor(VarCall &v, long long g0, int nb, const int *ncnt, const int *nidx,
+                              int2 *infob, bool &done) {
+  const TreeDesc *dtrees = S.tdesc.as<TreeDesc>();
+  const SolveConsts &c = v.c;
+  const int nz = v.nlev, nt = v.nt, list_cap = v.list_cap;
+  const bool handoff = handoff_path();
+  const size_t fwords = handoff ? big_factor_words(S.kp) : wave_factor_words(S.kp);
+  const size_t rec_bytes = handoff ? 8 * big_handoff_words(S.kp, 1) : 0;
+  long long Bs = nb;
+  if (handoff) {  // solve_batch_path's sub-batch of a single call
+    const long long fit = std::max<long long>(
+        kListLanes, (long long)(S.handoff_budget / rec_bytes) / kListLanes * kListLanes);
+    Bs = sub_batch(nb, std::min<long long>(S.big_sub, fit));
+  }
+  // (+1: the spare entry, as the record cache's regions have one)
+  if (S.wsf.ensure((size_t)(std::min<long long>(Bs, nb) + 1) * fwords * 8) != hipSuccess) {
+    (void)hipGetLastError();
+    CI.from_factor = 0;
+    CI.levels_per_wave = 0;
+    done = false;
+    return CWBL_OK;
+  }
+  if (handoff) HIPCHK(S.wsa.ensure((size_t)Bs * rec_bytes));
+  double *const fac = S.wsf.as<double>();
+  int kt;
+  for (long long s0 = 0; s0 < nb; s0 += Bs) {
+    const int ns = (int)std::min<long long>(Bs, nb - s0);
+    int2 *const inf = infob + s0;
+    HIPCHK(kt_begin(S.stream, &kt));
+    if (handoff) {
+      HIPCHK(launch_big_handoff(S.stream, S.kp, dtrees, c, v.sd, g0 + s0, ns, ncnt + s0 * nt,
+                                nidx + s0 * list_cap, inf, S.wsa.as<double>()));
+      HIPCHK(kt_end(S.stream, kt, KT_BIG_HANDOFF, ns));
+      HIPCHK(kt_begin(S.stream, &kt));
+      HIPCHK(launch_fill_tqb_tail(S.stream, S.kp, c, v.sd, g0 + s0, ns, S.wsa.as<double>(), inf,
+                                  fac));
+      HIPCHK(kt_end(S.stream, kt, KT_FILL_TQB_TAIL, ns));
+    } else {
+      HIPCHK(launch_fill_tq_wave(S.stream, S.kp, dtrees, c, v.sd, g0 + s0, ns, ncnt + s0 * nt,
+                                 nidx + s0 * list_cap, inf, fac));
+      HIPCHK(kt_end(S.stream, kt, KT_FILL_TQ_WAVE, ns));
+    }
+    const int lw = factor_levels_per_wave(ns, nz - 1);
+    CI.levels_per_wave = lw;
+    HIPCHK(kt_begin(S.stream, &kt));
+    if (handoff)
+      HIPCHK(launch_solve_tqb_factor_column(S.stream, S.kp, c, v.full, g0 + s0, ns, nz, lw, fac,
+                                            inf));
+    else
+      HIPCHK(launch_solve_tq_wave_factor_column(S.stream, S.kp, c, v.full, g0 + s0, ns, nz, lw,
+                                                fac, inf));
+    HIPCHK(kt_end(S.stream, kt,
+                  handoff ? KT_SOLVE_TQB_FACTOR_COLUMN : KT_SOLVE_TQ_WAVE_FACTOR_COLUMN,
+                  (long long)ns * (nz - 1)));
+  }
+  CI.from_factor = 1;
+  CI.chunk_launches = 0;
+  done = true;
+  return CWBL_OK;
+}
+
 // The solves of batch (g0, nb) of a column-shared call: g0 and nb count columns, the lists and
 // infob are the columns'.
 //   record path, option 1   assemble_record_kernel over the columns as it is, then
 //                           solve_tq40_column_kernel over the same records with the whole slab
+//   CWBL_OPT_COLUMN_FACTOR  (either option at k = 41..96) solve_batch_column_factor above; the
+//                           chunks below only if its workspace cannot be allocated
 //   chunked paths           (option 1 elsewhere, option 2 everywhere) the levels in chunks of up
 //                           to kMaxGroupVars: each chunk is the path's group launch on the column
 //                           view with var[i] = var + (kz0 + i) nx ny and the call's flags for
@@ -1911,6 +2013,11 @@ int solve_batch_column(VarCall &v, long long g0, int nb, const int *ncnt, const 
       v.lev = 1;
     }
   } restore{v, v.tv, v.sd, v.group};
+  if (column_factor_path()) {
+    bool done = false;
+    if (int rc = solve_batch_column_factor(v, g0, nb, ncnt, nidx, infob, done)) return rc;
+    if (done) return CWBL_OK;  // (else: no workspace, the chunks below)
+  }
   CI.chunk_launches = v.colshare == 1 && record_path() ? 0 : (nz + kMaxGroupVars - 1) / kMaxGroupVars;
   if (!record_path()) {
     for (int kz0 = 0; kz0 < nz; kz0 += kMaxGroupVars) {
@@ -2111,6 +2218,7 @@ int cwbl_init(const cwbl_init_params *p) {
   S.index_mode = 0;
   S.column_share = 0;
   S.column_levels = 0;
+  S.column_factor = false;
   S.factor_reuse = true;
   S.hit_merge = true;
   S.wave_reuse = false;
@@ -2138,12 +2246,21 @@ int cwbl_init(const cwbl_init_params *p) {
 int cwbl_set_option(int option, long long value) {
   if (!S.inited) return fail(CWBL_ERR_STATE, "cwbl_set_option before cwbl_init");
   auto range = [&](long long lo, long long hi) { return value >= lo && value <= hi; };
-  if (option == CWBL_OPT_HIT_MERGE || option == CWBL_OPT_HOST_PIPE) {
-    // how the cached batches are launched, or how a host slab travels, not what is cached: the
-    // generation stays
+  if (option == CWBL_OPT_HIT_MERGE || option == CWBL_OPT_HOST_PIPE ||
+      option == CWBL_OPT_COLUMN_FACTOR) {
+    // how the cached batches are launched, how a host slab travels, or how a shared call (which
+    // touches no cache) solves its levels, not what is cached: the generation stays
     if (!range(0, 1))
       return fail(CWBL_ERR_ARG, "cwbl_set_option: value %lld out of range for option %d", value,
                   option);
+    if (option == CWBL_OPT_COLUMN_FACTOR) {
+      S.column_factor = value == 1;
+      if (!S.column_factor) {  // off holds no memory
+        (void)hipStreamSynchronize(S.stream);
+        S.wsf.release();
+      }
+      return CWBL_OK;
+    }
     (option == CWBL_OPT_HIT_MERGE ? S.hit_merge : S.host_pipe) = value == 1;
     return CWBL_OK;
   }

@@ -505,6 +505,21 @@ hipError_t launch_fill_tqb_tail_rows(hipStream_t s, SolveConsts c, SlabDev slab,
 hipError_t launch_solve_tqb_factor_rows(hipStream_t s, SolveConsts c, SlabDev slab, long long g0,
                                         int npts, const double *fac, int2 *info);
 
+// A column-shared call's levels from kept factors (CWBL_OPT_COLUMN_FACTOR): the fill above has
+// analysed level 0 of the ncol columns from g0 on the column view and left their factors at
+// `fac` and their accepted counts in info[i].x; these solve the levels 1 .. nz-1 of every column
+// from its factor, one column per wavefront and lw levels per wavefront (grid (ncol,
+// ceil((nz - 1) / lw)); the bits do not depend on lw).  slab is the whole slab (nz levels);
+// info is read only.  cwbl_tq_wave_column.hip (KP = 48, 56, 64: solve_tq_wave_factor_kernel's
+// replay and tq_wave_finish per level) and cwbl_tq_big_column.hip (KP = 96: tqb_factor_hit per
+// level).
+hipError_t launch_solve_tq_wave_factor_column(hipStream_t s, int kp, SolveConsts c, SlabDev slab,
+                                              long long g0, int ncol, int nz, int lw,
+                                              const double *fac, const int2 *info);
+hipError_t launch_solve_tqb_factor_column(hipStream_t s, int kp, SolveConsts c, SlabDev slab,
+                                          long long g0, int ncol, int nz, int lw,
+                                          const double *fac, const int2 *info);
+
 // KP = 96, 128: one 256-thread workgroup per point (cwbl_tq_big.hip)
 hipError_t launch_solve_tq_big(hipStream_t s, int kp, bool assembled, const TreeDesc *trees,
                                SolveConsts c, SlabDev slab, long long g0, int npts,

@@ -14,157 +14,9 @@
 // step, in the order of first use, one column per register, unconditionally (the lane mask is
 // applied at the use), so that each step's s_waitcnt counts the loads behind its own: the chain
 // then waits for the memory's latency once, at step 0, and for bandwidth after that.
-#include "cwbl_tq_common.h"
+#include "cwbl_tq_wave.h"
 
 namespace cwbl {
-
-// What follows the Householder loop in solve_tq_kernel, from the quadrature level to the
-// stores: sm.tq, sm.tau and the packed vectors in sm.u.reg[0, NHV) are as the loop leaves them.
-template <int KP>
-__device__ __forceinline__ void tq_wave_finish(TqSmem<KP> &sm, const SolveConsts &c,
-                                               const SlabDev &slab, int gi, int lane, int k,
-                                               long long P, float xbl, double xb_mean,
-                                               double trace, int ptot, int2 *__restrict__ info) {
-  using SM = TqSmem<KP>;
-  constexpr int H = KP / 2;
-  double *Ym = &sm.u.reg[SM::NHV], *Zm = Ym + KP;
-  // ---- T^-1/2 u2 by quadrature, u1^T T^-1 u2 exactly --------------------------------------
-  const double m = (double)c.inflat;
-  const double ratio = trace / m - (double)(k - 1);
-  int level = 1;
-  double dec = 10.0;
-  while (level < kQuadLevels && dec < ratio) {
-    dec *= 10.0;
-    ++level;
-  }
-  const int node = lane & 31, side = lane >> 5;
-  const int npass = quad_passes(level);
-  const double2 *rule = quad_rule(c.quad_r, npass == 1 ? 4 : 8, level);
-  const unsigned q0 = side ? (KP - 1) * 32u : 0u, dirb = side ? (unsigned)-32 : 32u;
-  const unsigned csb = side ? 40u : 8u;
-  double *ym = Ym + side * H, *zm = Zm + side * H;
-  for (int pass = 0; pass < npass; ++pass) {
-    const bool exact = pass == 0 && node == 31;
-    double sigma = 0.0, omega = 0.0;
-    if (!exact) {
-      const double2 tw = rule[31 * pass + node];
-      sigma = m * tw.x;
-      omega = sqrt(m) * tw.y;
-    }
-    double hh[H], mm[H];
-    double dl = lds_at(sm.tq, q0) + sigma;
-    double gt = lds_at(sm.tq, q0 + 24);
-    double rdl = rcp64(dl);
-#pragma unroll
-    for (int t = 1; t < H; ++t) {
-      const unsigned o = opaque_after(q0, dl) + dirb * (unsigned)t;
-      const double ct = lds_at(sm.tq, o + csb);
-      const double l = ct * rdl;
-      hh[t - 1] = gt * rdl;
-      mm[t - 1] = l;  // = c_t / dl_{t-1}
-      asm volatile("" : "+v"(hh[t - 1]));  // materialise now: g_{t-1} and 1/dl_{t-1} die here
-      dl = fma(-l, ct, lds_at(sm.tq, o) + sigma);
-      gt = fma(-l, gt, lds_at(sm.tq, o + 24));
-      rdl = rcp64(dl);
-      __builtin_amdgcn_sched_barrier(0);  // keep the recurrence in order: bounded live ranges
-    }
-    // meeting rows H-1 (top) and H (bottom): 2x2 solve with the partner lane's pivot
-    const double cm = sm.tq[H][1];
-    const double dlo = __shfl_xor(dl, 32, 64), go = __shfl_xor(gt, 32, 64);
-    double xv = (gt * dlo - cm * go) / fma(dl, dlo, -cm * cm);
-    {
-      const double ys = half_sum_dpp(omega * xv);
-      if (node == 0) ym[H - 1] = pass ? ym[H - 1] + ys : ys;
-      if (exact) zm[H - 1] = xv;
-    }
-#pragma unroll
-    for (int t = H - 2; t >= 0; --t) {
-      xv = fma(-mm[t], xv, hh[t]);
-      const double ys = half_sum_dpp(omega * xv);
-      if (node == 0) ym[t] = pass ? ym[t] + ys : ys;
-      if (exact) zm[t] = xv;
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-  __syncthreads();
-  const int wi = lane < H ? lane : H + (KP - 1 - lane);  // walk slot of row `lane`
-  const double zl = lane < KP ? Zm[wi] : 0.0;
-  double yl = lane < KP ? Ym[wi] : 0.0;
-  const double d = wave_sum_dpp(lane < KP ? sm.tq[lane][2] * zl : 0.0);  // u1 . T^-1 u2
-
-  // ---- back-transform: y <- Q y = H_0 H_1 ... H_{k-3} y, two reflectors per reduction ----
-  auto hvec = [&](int j) {
-    const int off = j * (k - 1) - j * (j - 1) / 2;
-    return (lane > j && lane < k) ? sm.u.reg[off + lane - (j + 1)] : 0.0;
-  };
-  int j = k - 3;
-  for (; j >= 1; j -= 2) {
-    const double t1 = sm.tau[j], t0 = sm.tau[j - 1];
-    // a reflector with tau = 0 was never stored (H = I): use a zero vector
-    const double v1 = t1 == 0.0 ? 0.0 : hvec(j), v0 = t0 == 0.0 ? 0.0 : hvec(j - 1);
-    double a1 = v1 * yl, b0 = v0 * yl, c01 = v0 * v1, pad = 0.0;
-    wave_sum4_dpp(a1, b0, c01, pad);
-    yl = fma(-t1 * a1, v1, yl);
-    yl = fma(-t0 * fma(-t1 * a1, c01, b0), v0, yl);
-  }
-  if (j == 0 && sm.tau[0] != 0.0) {
-    const double v0 = hvec(0);
-    const double s0 = wave_sum_dpp(v0 * yl);
-    yl = fma(-sm.tau[0] * s0, v0, yl);
-  }
-  const double sk = sqrt((double)(k - 1));
-  // analysis of member `lane` (xa = wbar, :675-679); fp32 from here on, in registers
-  float xal = lane < KP ? (float)(xb_mean + (d + sk * yl)) : 0.0f;
-
-  // ---- RTPP / RTPS (:684-698), fp32 in the reference's order -------------------------
-  auto seq_sum = [&](float x) {
-    float s = 0.0f;
-    for (int mm = 0; mm < k; ++mm) s = s + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), mm));
-    return s;
-  };
-  if (c.use_rtpp || c.use_rtps) {
-    const float xa_mean = seq_sum(xal) * c.nmember_inv;
-    const double xpl = lane < k ? (double)xbl - xb_mean : 0.0;
-    float xap = 0.0f;
-    if (lane < k) {
-      xap = xal - xa_mean;
-      if (c.use_rtpp)
-        xap = (float)((double)((1.0f - c.rtpp_alpha) * xap) + (double)c.rtpp_alpha * xpl);
-    }
-    if (c.use_rtps) {
-      double d8 = 0.0;
-      for (int mm = 0; mm < k; ++mm) {
-        const double xp = readlane_f64(xpl, mm);
-        d8 = d8 + xp * xp;
-      }
-      const float xb_std = (float)d8;
-      const float xa_std = seq_sum(xap * xap);
-      xap = xap * (c.rtps_alpha * sqrtf(xb_std / xa_std) - c.rtps_alpha + 1.0f);
-    }
-    xal = xa_mean + xap;
-  }
-
-  if (lane < k) slab.var[P + slab.L * lane] = xal;
-  // info.y: decade of the quadrature rule (negative when M/m exceeds the last table)
-  if (lane == 0 && info) info[gi] = make_int2(ptot, ratio > dec ? -level : level);
-}
-
-// var index of member 0 of point g
-__device__ __forceinline__ long long wave_point_index(const SlabDev &slab, long long g) {
-  const int i = (int)(g % slab.ix_lim);
-  const long long r = g / slab.ix_lim;
-  const int j = (int)(r % slab.iy_lim);
-  const int kz = (int)(r / slab.iy_lim);
-  return i + (long long)slab.nx * (j + (long long)slab.ny * kz);
-}
-
-// xb_mean = sum(xb) * nmember_inv in fp32 (:671), sequential like the reference
-__device__ __forceinline__ double wave_xb_mean(float xbl, int k, float nmember_inv) {
-  float s = 0.0f;
-  for (int mm = 0; mm < k; ++mm)
-    s = s + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(xbl), mm));
-  return (double)(s * nmember_inv);
-}
 
 // fac: the WaveFactor<KP> of point gi of the launch at fac + gi WORDS.  A point with p = 0
 // writes none (a hit leaves at its info); a step that leaves early (j >= k - 2) or is the
@@ -413,7 +265,15 @@ fill_tq_wave_kernel(const TreeDesc *__restrict__ trees, SolveConsts c, SlabDev s
     f[F::U1 + lane] = ub;
     f[F::TAU + lane] = sm.tau[lane];
   }
-  tq_wave_finish<KP>(sm, c, slab, gi, lane, k, P, xbl, xb_mean, trace, ptot, info);
+  // the quadrature level, from the spectrum bound M / m = trace / inflat - (k - 1)
+  const double ratio = trace / (double)c.inflat - (double)(k - 1);
+  int level = 1;
+  double dec = 10.0;
+  while (level < kQuadLevels && dec < ratio) {
+    dec *= 10.0;
+    ++level;
+  }
+  tq_wave_finish<KP>(sm, c, slab, gi, lane, k, P, xbl, xb_mean, ratio, level, dec, ptot, info);
 }
 
 // One point per wavefront from its WaveFactor.  info[gi].x is the accepted count the fill left
@@ -495,7 +355,15 @@ solve_tq_wave_factor_kernel(SolveConsts c, SlabDev slab, long long g0, int npts,
   double trace = 0.0;
   for (int j = 0; j < k; ++j) trace += readlane_f64(dv, j);
   __syncthreads();
-  tq_wave_finish<KP>(sm, c, slab, gi, lane, k, P, xbl, xb_mean, trace, ptot, info);
+  // the quadrature level, from the spectrum bound M / m = trace / inflat - (k - 1)
+  const double ratio = trace / (double)c.inflat - (double)(k - 1);
+  int level = 1;
+  double dec = 10.0;
+  while (level < kQuadLevels && dec < ratio) {
+    dec *= 10.0;
+    ++level;
+  }
+  tq_wave_finish<KP>(sm, c, slab, gi, lane, k, P, xbl, xb_mean, ratio, level, dec, ptot, info);
 }
 
 hipError_t launch_fill_tq_wave(hipStream_t s, int kp, const TreeDesc *trees, SolveConsts c,

@@ -31,6 +31,7 @@ OPT_BIG_PATH, OPT_BIG_BATCH, OPT_PAGEABLE, OPT_BIN_DIV, OPT_LEAD_DIV, OPT_MAX_BA
 OPT_INFO_WINDOW, OPT_INDEX, OPT_RECORD_REUSE = 12, 13, 14
 OPT_COLUMN_SHARE, OPT_COLUMN_LEVELS, OPT_FACTOR_REUSE, OPT_HIT_MERGE = 15, 16, 17, 18
 OPT_WAVE_REUSE, OPT_HOST_PIPE, OPT_BIG_REUSE, OPT_ROWS_REUSE = 19, 20, 21, 22
+OPT_COLUMN_FACTOR = 23
 OPTIONS = {"solver": OPT_SOLVER, "split40": OPT_SPLIT40, "split40_batch": OPT_SPLIT40_BATCH,
            "search": OPT_SEARCH,
            "big_path": OPT_BIG_PATH, "big_batch": OPT_BIG_BATCH, "pageable": OPT_PAGEABLE,
@@ -40,7 +41,7 @@ OPTIONS = {"solver": OPT_SOLVER, "split40": OPT_SPLIT40, "split40_batch": OPT_SP
            "column_levels": OPT_COLUMN_LEVELS, "factor_reuse": OPT_FACTOR_REUSE,
            "hit_merge": OPT_HIT_MERGE, "wave_reuse": OPT_WAVE_REUSE,
            "host_pipe": OPT_HOST_PIPE, "big_reuse": OPT_BIG_REUSE,
-           "rows_reuse": OPT_ROWS_REUSE}
+           "rows_reuse": OPT_ROWS_REUSE, "column_factor": OPT_COLUMN_FACTOR}
 
 #: cwbl_column_info_t.reason
 (COLUMN_SHARED, COLUMN_REASON_OFF, COLUMN_REASON_3D, COLUMN_REASON_Q1, COLUMN_REASON_NZ,
@@ -138,10 +139,10 @@ class ReuseInfo(C.Structure):
 class ColumnInfo(C.Structure):
     _fields_ = [("shared", C.c_int), ("reason", C.c_int), ("columns", C.c_longlong),
                 ("levels", C.c_int), ("levels_per_wave", C.c_int), ("chunk_launches", C.c_int),
-                ("reserved", C.c_int)]
+                ("from_factor", C.c_int)]
 
     def as_dict(self):
-        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+        return {name: getattr(self, name) for name, _ in self._fields_}
 
 
 class TransferInfo(C.Structure):

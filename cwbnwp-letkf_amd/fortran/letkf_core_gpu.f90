@@ -92,6 +92,9 @@ module letkf_core_gpu
     ! cwbl_set_option: calls of one variable at k = 97..128 keep each point's factor for the next
     ! call with the same localisation (1; 0, default: off), within CWBL_OPT_RECORD_REUSE's budget
     integer(c_int), parameter, public :: CWBL_OPT_ROWS_REUSE = 22
+    ! cwbl_set_option: a column-shared call at k = 41..96 solves every level from one kept factor
+    ! per column (1; 0, default: the levels run as group launches of eight)
+    integer(c_int), parameter, public :: CWBL_OPT_COLUMN_FACTOR = 23
     ! cwbl_set_option: host-memory slabs of group calls, column-shared calls and calls with
     ! tune_q = 1 travel batch by batch under the solves (1; 0, default: whole, around them)
     integer(c_int), parameter, public :: CWBL_OPT_HOST_PIPE = 20
@@ -120,7 +123,7 @@ module letkf_core_gpu
     type, bind(C), public :: cwbl_column_info_t    ! cwbl_column_info
         integer(c_int)       :: shared, reason
         integer(c_long_long) :: columns
-        integer(c_int)       :: levels, levels_per_wave, chunk_launches, reserved
+        integer(c_int)       :: levels, levels_per_wave, chunk_launches, from_factor
     end type cwbl_column_info_t
 
     type, bind(C), public :: cwbl_transfer_info_t  ! cwbl_transfer_info

@@ -449,7 +449,7 @@ enum {
                                 * (k <= 64, CWBL_OPT_BIG_PATH = 0).  Group calls and
                                 * column-shared calls neither read, fill nor invalidate the
                                 * cache */
-  CWBL_OPT_ROWS_REUSE = 22     /* 1: cwbl_analyze_var on the hand-off path at k = 97..128
+  CWBL_OPT_ROWS_REUSE = 22,    /* 1: cwbl_analyze_var on the hand-off path at k = 97..128
                                 * (KP = 128, default solver, CWBL_OPT_BIG_PATH = 1) keeps each
                                 * point's factor A = Q T Q^T for the next call, as
                                 * CWBL_OPT_BIG_REUSE does at KP = 96 and within the same
@@ -466,6 +466,30 @@ enum {
                                 * k <= 96 and under CWBL_OPT_BIG_PATH = 0.  Group calls and
                                 * column-shared calls neither read, fill nor invalidate the
                                 * cache */
+  CWBL_OPT_COLUMN_FACTOR = 23  /* 1: a call that is shared per column (CWBL_OPT_COLUMN_SHARE 1
+                                * or 2, eligible as there) on the one-wavefront path at
+                                * k = 41..64 or on the hand-off path at k = 65..96 solves every
+                                * level from one kept factor per column instead of running the
+                                * levels as group launches of eight.  Per (sub-)batch of
+                                * columns the factor cache's fill kernel analyses level 0 and
+                                * leaves each column's factor A = Q T Q^T (the WaveFactor or
+                                * BigFactor of CWBL_OPT_WAVE_REUSE and CWBL_OPT_BIG_REUSE) in a
+                                * workspace of the call, and one launch of
+                                * solve_tq_wave_factor_column_kernel<KP> or
+                                * solve_tqb_factor_column_kernel<96, 32> solves the levels
+                                * 1 .. nz-1 from it, CWBL_OPT_COLUMN_LEVELS levels per wavefront
+                                * (0: automatic).  Bit-identical results and equal counters,
+                                * whatever the level split.  The workspace is a grow-only device
+                                * buffer of one (sub-)batch's factors (KP (KP - 1) / 2 + 5 KP
+                                * fp64 words per column at most); nothing is kept between
+                                * calls, and the record cache is neither read, filled nor
+                                * invalidated.  If the workspace cannot be allocated the call
+                                * runs the level chunks; that is no error.  0 (default): the
+                                * shared call runs as without the option and no memory is
+                                * taken.  Accepted and ignored everywhere else: k <= 40,
+                                * k = 97..128, CWBL_OPT_SOLVER = 1, CWBL_OPT_BIG_PATH = 0, group
+                                * calls and calls that are not shared.  Nothing that is cached
+                                * depends on it: setting it leaves a filled cache valid */
 };
 int         cwbl_set_option(int option, long long value);
 
@@ -550,12 +574,15 @@ typedef struct cwbl_column_info_t {
   int       reason;           /* CWBL_COLUMN_REASON_* when not shared, else CWBL_COLUMN_SHARED */
   long long columns;          /* ix_lim * iy_lim (0 when not shared) */
   int       levels;           /* nz (0 when not shared) */
-  int       levels_per_wave;  /* solve_tq40_column_kernel: levels per wavefront of the last
-                               * launch; 0 on the chunked paths */
+  int       levels_per_wave;  /* solve_tq40_column_kernel, or the level kernel of
+                               * CWBL_OPT_COLUMN_FACTOR (over the levels 1 .. nz-1): levels per
+                               * wavefront of the last launch; 0 on the chunked paths */
   int       chunk_launches;   /* chunked paths: launches per (sub-)batch, one per chunk of up
                                * to CWBL_MAX_GROUP_VARS levels (a remainder of one level runs
-                               * the single kernel and counts); 0 for the column kernel */
-  int       reserved;
+                               * the single kernel and counts); 0 for the column kernel and
+                               * when from_factor is 1 */
+  int       from_factor;      /* 1: the levels were solved from one kept factor per column
+                               * (CWBL_OPT_COLUMN_FACTOR) */
 } cwbl_column_info_t;
 int         cwbl_column_info(cwbl_column_info_t *out);
 

@@ -9,6 +9,8 @@ modes alternated --rounds times:
   0   this tree's library, column_share = 0: the per-point call
   1   column_share = 1: the column kernel (k = 17..40) or the level-chunked group kernels
   2   column_share = 2: the level-chunked group kernels on the record path too
+  F   (--factor, in mode 2's place) column_share = 1 with column_factor = 1: every level from
+      one kept factor per column (k = 41..96); the output goes to profiles/column_factor.txt
 
 Every mode runs with record_reuse = 0 (a shared call runs without the cache; the per-point
 call then pays no cache fill either).  Per mode and round: one library state, one untimed
@@ -17,10 +19,13 @@ repetition (it sizes every buffer), then --reps timed ones; each restores the va
 two device synchronisations.  Printed per k: median and min-max per mode over both rounds, the
 SHA-256 of the analysed slab (it must agree across all modes), column_info, the kernel_times
 of one further repetition per mode, the ratios of modes 1 and 2 to mode 0 of the same session,
-and whether P and 0 agree within their run-to-run ranges (option 0 costs nothing).
+and whether P and 0 agree within their run-to-run ranges (option 0 costs nothing).  With
+--factor also mode F / mode 1 and whether F is faster than 1 by more than either mode's
+run-to-run range (the bar of the option's eligibility at that k).
 
   python scripts/column_share_ab.py [--ks 40,64,96] [--nz 50] [--reps 3] [--rounds 2]
                                     [--parent DIR/libcwbl.so] [--scale S] [--out FILE]
+                                    [--factor]
 """
 import argparse
 import hashlib
@@ -62,10 +67,12 @@ class Bench:
 
     def run(self, lib, share, reps, digest, kernels):
         """-> (ms per repetition, SHA-256 of the analysis or None, column_info or None,
-        kernel_times of one further repetition or None)"""
+        kernel_times of one further repetition or None).  share "F": 1 with column_factor."""
         torch, w = self.torch, self.w
         opts = {"record_reuse": 0}
-        if share is not None:
+        if share == "F":
+            opts.update(column_share=1, column_factor=1)
+        elif share is not None:
             opts["column_share"] = share
         core = abi.Core(w.k, device=0, lib=lib, options=opts)
 
@@ -103,10 +110,15 @@ def main():
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--parent", default=None, help="the parent commit's libcwbl.so (mode P)")
     ap.add_argument("--scale", type=float, default=None, help="shrink the grid (a quick look)")
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "column_share.txt"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--factor", action="store_true", help="mode F in mode 2's place")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(REPO, "profiles",
+                                "column_factor.txt" if args.factor else "column_share.txt")
     here = abi.load_library()
-    modes = [("0", here, 0), ("1", here, 1), ("2", here, 2)]
+    modes = [("0", here, 0), ("1", here, 1),
+             ("F", here, "F") if args.factor else ("2", here, 2)]
     if args.parent:
         # (the parent lacks this change's entry points: the prototypes of those it has)
         import ctypes
@@ -117,7 +129,8 @@ def main():
                 fn.argtypes, fn.restype = ours.argtypes, ours.restype
         modes.insert(0, ("P", parent, None))
     what = {"P": "parent commit's library", "0": "column_share = 0 (per point)",
-            "1": "column_share = 1", "2": "column_share = 2 (level chunks)"}
+            "1": "column_share = 1", "2": "column_share = 2 (level chunks)",
+            "F": "column_share = 1, column_factor = 1"}
     for k in (int(s) for s in args.ks.split(",")):
         w = synth.make("c2", k=k, nz=args.nz, vclr=-1.0, scale=args.scale)
         say(f"== c2, vclr = -1: {w.nx}x{w.ny}x{w.nz} grid = {w.points} points, k={k}, "
@@ -146,12 +159,20 @@ def main():
         shas = {r["sha"] for r in res.values()}
         say(f"   analyses bit-equal across the modes: {len(shas) == 1}")
         m0 = float(np.median(res["0"]["ms"]))
-        for m in ("1", "2"):
+        last = modes[-1][0]  # "2" or "F"
+        for m in ("1", last):
             mm = float(np.median(res[m]["ms"]))
             say(f"   mode {m} / mode 0 = {mm / m0:.3f}  ({'below' if mm < 0.5 * m0 else 'NOT below'} "
                 f"half of mode 0)")
-        m1, m2 = (float(np.median(res[m]["ms"])) for m in ("1", "2"))
-        say(f"   mode 1 / mode 2 = {m1 / m2:.3f}")
+        m1, m2 = (float(np.median(res[m]["ms"])) for m in ("1", last))
+        if args.factor:
+            one, fac = res["1"]["ms"], res["F"]["ms"]
+            rng = max(max(one) - min(one), max(fac) - min(fac))
+            say(f"   mode F / mode 1 = {m2 / m1:.3f}; median 1 - median F = {m1 - m2:.3f} ms, "
+                f"run-to-run range {rng:.3f} ms: F is "
+                f"{'faster' if m1 - m2 > rng else 'NOT faster'} by more than the range")
+        else:
+            say(f"   mode 1 / mode 2 = {m1 / m2:.3f}")
         if "P" in res:
             p, z = res["P"]["ms"], res["0"]["ms"]
             gap = abs(float(np.median(p) - np.median(z)))
