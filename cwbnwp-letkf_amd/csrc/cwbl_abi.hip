@@ -228,6 +228,7 @@ enum KernelId {
   KT_BIG_HANDOFF_MULTI8, KT_TQB_TAIL_MULTI2, KT_TQB_TAIL_MULTI4, KT_TQB_TAIL_MULTI8,
   KT_SOLVE_TQ, KT_FILL_TQ_WAVE, KT_SOLVE_TQ_WAVE_FACTOR, KT_SOLVE_TQ_BIG, KT_SOLVE_JACOBI,
   KT_TUNE_Q, KT_SOLVE_TQ_WAVE_FACTOR_COLUMN, KT_SOLVE_TQB_FACTOR_COLUMN,
+  KT_SOLVE_TQ_WAVE_FACTOR_COLUMN_ALL, KT_SOLVE_TQB_FACTOR_COLUMN_ALL,
   KT_COUNT
 };
 struct KTime { long long launches = 0, points = 0; double ms = 0.0; };
@@ -294,6 +295,57 @@ struct RecordCache {
     plan.clear();
     off.clear();
     pts = 0;
+  }
+};
+
+// The column cache (CWBL_OPT_COLUMN_REUSE): what a column-shared call keeps per COLUMN of its
+// leading column batches, for the next shared call of the same localisation on the same x and y,
+// whatever its nz, alt and epilogue flags (MU, P, PH).  The record cache above is per point and
+// a column call never touches it; a per-point call never touches this one.
+//   form        path                       a cached column      a fill; a hit
+//   Records     k = 17..40                 AsmRecord<40>        assemble_record_kernel into the
+//                                                               region, solve_tq40_column_kernel;
+//                                                               the latter alone
+//   WaveFactor  k = 41..64                 WaveFactor<KP>       fill_tq_wave_kernel (level 0) and
+//                                                               the level kernel from level 1;
+//                                                               the all-levels kernel
+//   BigFactor   k = 65..96                 BigFactor<96, 32>    the hand-off kernel,
+//                                                               fill_tqb_tail_kernel and the level
+//                                                               kernel from level 1; the
+//                                                               all-levels kernel
+// The key has no nz, alt_nx or alt_ny: a 2-D tree reads neither the level nor alt.
+struct ColumnKey {
+  unsigned long long gen;  // State::gen: obs set, cwbl_init constants, options
+  int kp;
+  float multi_infl;
+  int dims[4];             // nx, ny, ix_lim, iy_lim
+  cwbl_type_params gts[CWBL_NUM_GTS_TYPES], radar[CWBL_NUM_RADAR_TYPES];
+};
+struct ColumnCache {
+  bool valid = false;  // a fill completed: everything below describes it
+  ColumnKey key{};
+  // Batch b < off.size() of `plan` keeps its nb entries and a spare one from word off[b] of
+  // `rec`, sub-batch s0 of it s0 entries on (RecordCache's layout).  info: (p, level) of the
+  // `cols` cached columns as the fill left them.  sx, sy: the coordinates of the fill.
+  DevBuf rec, info, sx, sy, flag;
+  PinBuf hflag;
+  CacheForm form = CacheForm::None;
+  std::vector<std::pair<long long, int>> plan;
+  std::vector<size_t> off;
+  long long cols = 0;
+  size_t nxy = 0;
+  // what a call that skips plan_trees and the searches still reports (lz_truncated: per level)
+  int nt = 0, list_cap = 0;
+  long long lz_truncated = 0;
+  size_t bytes() const { return rec.n + info.n + sx.n + sy.n + flag.n; }
+  void release() {
+    valid = false;
+    form = CacheForm::None;
+    for (DevBuf *b : {&rec, &info, &sx, &sy, &flag}) b->release();
+    hflag.release();
+    plan.clear();
+    off.clear();
+    cols = 0;
   }
 };
 
@@ -374,7 +426,9 @@ struct State {
   bool column_factor = false;     // CWBL_OPT_COLUMN_FACTOR: a shared call's levels from one kept
                                   // factor per column (k = 41..96)
   int ncu = 0;                    // compute units of the device (automatic level split)
+  size_t column_reuse = 0;        // CWBL_OPT_COLUMN_REUSE in bytes (0: off)
   RecordCache cache;
+  ColumnCache ccache;
   // pageable host slabs: each batch's var columns go through page-locked bounce slots (two
   // in, two out), filled and drained by a few host threads while the GPU runs other batches
   static constexpr int kSlots = 3;
@@ -563,6 +617,11 @@ std::string kernel_name(int id) {
     case KT_SOLVE_TQB_FACTOR_COLUMN:
       return "solve_tqb_factor_column_kernel<" + kp + ", " + std::to_string(big_split_j0(S.kp)) +
              ">";
+    case KT_SOLVE_TQ_WAVE_FACTOR_COLUMN_ALL:
+      return "solve_tq_wave_factor_column_all_kernel<" + kp + ">";
+    case KT_SOLVE_TQB_FACTOR_COLUMN_ALL:
+      return "solve_tqb_factor_column_all_kernel<" + kp + ", " +
+             std::to_string(big_split_j0(S.kp)) + ">";
   }
   return "?";
 }
@@ -646,6 +705,7 @@ int bin_div_for(const HostTree &t, int dim) {
 
 cwbl_reuse_info_t R;  // cwbl_reuse_info: what the current cwbl_analyze_var reused
 cwbl_column_info_t CI;  // cwbl_column_info: what it shared per column (CWBL_OPT_COLUMN_SHARE)
+cwbl_column_reuse_info_t CR;  // cwbl_column_reuse_info: what it did with the column cache
 cwbl_transfer_info_t TI;  // cwbl_transfer_info: how it moved a host slab's var
 
 // ---- cwbl_prep_info: what the current cwbl_analyze_var spends on its search index -----------
@@ -985,6 +1045,7 @@ void release_all() {
   S.ix_pin.release();
   S.hitseg_pin.release();
   S.cache.release();
+  S.ccache.release();
   for (hipEvent_t e : S.pevents) (void)hipEventDestroy(e);
   S.pevents.clear();
   g_pspans.clear();
@@ -1105,6 +1166,9 @@ struct VarCall {
   int reuse = 0;
   long long ncached = 0;
   bool full_hit = false;
+  // the cache that reuse, ncached and full_hit speak of is the column cache
+  // (CWBL_OPT_COLUMN_REUSE: a column-shared call), not the record cache
+  bool colcache = false;
   // CWBL_OPT_HIT_MERGE: the call's cached batches go out in one launch per info window;
   // hitseg_used: entries of S.hitseg_pin taken by the launches so far
   bool merge = false;
@@ -1236,18 +1300,22 @@ int begin_fill(VarCall &v, const RecordKey &key, CacheForm form) {
 // The info window that opens at point g on a hit: the cached points' accepted counts, which
 // solve_tq40_kernel reads where the assembly would have left them.
 int restore_info(VarCall &v, long long g) {
-  const long long n = std::min<long long>(v.info_cap, S.cache.pts - g);
+  const long long pts = v.colcache ? S.ccache.cols : S.cache.pts;
+  const int2 *const kept = (v.colcache ? S.ccache.info : S.cache.info).as<int2>();
+  const long long n = std::min<long long>(v.info_cap, pts - g);
   if (v.reuse != 2 || n <= 0) return CWBL_OK;
-  HIPCHK(hipMemcpyAsync(S.info.p, S.cache.info.as<int2>() + g, (size_t)n * sizeof(int2),
+  HIPCHK(hipMemcpyAsync(S.info.p, kept + g, (size_t)n * sizeof(int2),
                         hipMemcpyDeviceToDevice, S.stream));
   return CWBL_OK;
 }
 
 // The info window [v.win0, end) as a fill's solves left it (p is what the assembly wrote).
 int keep_info(VarCall &v, long long end) {
-  const long long n = std::min<long long>(end, S.cache.pts) - v.win0;
+  const long long pts = v.colcache ? S.ccache.cols : S.cache.pts;
+  int2 *const kept = (v.colcache ? S.ccache.info : S.cache.info).as<int2>();
+  const long long n = std::min<long long>(end, pts) - v.win0;
   if (v.reuse != 1 || n <= 0) return CWBL_OK;
-  HIPCHK(hipMemcpyAsync(S.cache.info.as<int2>() + v.win0, S.info.p, (size_t)n * sizeof(int2),
+  HIPCHK(hipMemcpyAsync(kept + v.win0, S.info.p, (size_t)n * sizeof(int2),
                         hipMemcpyDeviceToDevice, S.stream));
   return CWBL_OK;
 }
@@ -1838,6 +1906,93 @@ int solve_batch_path(VarCall &v, long long g0, int nb, const int *ncnt, const in
   return CWBL_OK;
 }
 
+// ---- CWBL_OPT_COLUMN_REUSE ---------------------------------------------------------------------
+// The classes whose column-shared calls fill and read the column cache: the paths with a
+// per-column form and a kernel that solves every level from it.  Accepted and ignored elsewhere
+// (k <= 16, CWBL_OPT_SPLIT40 = 0, CWBL_OPT_SOLVER = 1, CWBL_OPT_BIG_PATH = 0, k = 97..128).
+bool column_reuse_path() {
+  return S.column_reuse > 0 && S.column_share != 0 &&
+         (record_path() || (wave_path() && S.kp > kTq4KP) || (handoff_path() && S.kp == 96));
+}
+CacheForm column_form() {
+  return record_path() ? CacheForm::Records
+         : wave_path() ? CacheForm::WaveFactor
+                       : CacheForm::BigFactor;
+}
+
+void make_column_key(ColumnKey &key, const cwbl_var_params *vp, const cwbl_slab *sl) {
+  std::memset(&key, 0, sizeof key);
+  key.gen = S.gen;
+  key.kp = S.kp;
+  key.multi_infl = vp->multi_infl;
+  const int dims[4] = {sl->nx, sl->ny, sl->ix_lim, sl->iy_lim};
+  std::memcpy(key.dims, dims, sizeof dims);
+  std::memcpy(key.gts, vp->gts, sizeof key.gts);
+  std::memcpy(key.radar, vp->radar, sizeof key.radar);
+}
+
+// The hit test behind an equal key: x and y of the slab (staged copies for a host slab) against
+// the fill's snapshot, exactly.  alt is not compared: a 2-D tree never reads it.  One flag read
+// back, one synchronisation of S.stream.
+int column_coords_match(VarCall &v, bool &same) {
+  ColumnCache &C = S.ccache;
+  const auto t0 = std::chrono::steady_clock::now();
+  int *flag = C.flag.as<int>();
+  HIPCHK(hipMemsetAsync(flag, 0, sizeof(int), S.stream));
+  HIPCHK(launch_coord_snapshot(S.stream, false, v.sd.x, C.sx.as<float>(), (long long)C.nxy, flag));
+  HIPCHK(launch_coord_snapshot(S.stream, false, v.sd.y, C.sy.as<float>(), (long long)C.nxy, flag));
+  HIPCHK(hipMemcpyAsync(C.hflag.p, flag, sizeof(int), hipMemcpyDeviceToHost, S.stream));
+  HIPCHK(hipStreamSynchronize(S.stream));
+  same = *C.hflag.as<int>() == 0;
+  CR.ms_compare = ms_since(t0);
+  return CWBL_OK;
+}
+
+// A shared call that does not hit: plans which leading column batches fit the budget, allocates
+// their regions (kept from an earlier fill when large enough) and takes the snapshot of x and y.
+// The batches then assemble, or fill their factors, into their own regions.  Nothing fits, or an
+// allocation fails: no error, nothing is held and the call runs without the cache.
+int begin_column_fill(VarCall &v, const ColumnKey &key) {
+  ColumnCache &C = S.ccache;
+  C.valid = false;
+  C.key = key;
+  C.plan = v.plan;
+  C.off.clear();
+  C.cols = 0;
+  C.form = column_form();
+  const size_t w = form_words(C.form, S.kp);
+  size_t words = 0;
+  for (const auto &b : v.plan) {
+    const size_t need = ((size_t)b.second + 1) * w;  // (+1: the spare entry)
+    if ((words + need) * sizeof(double) > S.column_reuse) break;
+    C.off.push_back(words);
+    words += need;
+    C.cols += b.second;
+  }
+  if (C.off.empty()) {
+    C.release();
+    return CWBL_OK;
+  }
+  C.nxy = (size_t)v.sl->nx * v.sl->ny;
+  // grow-only, with 1/16 of headroom within the budget (begin_fill)
+  const size_t need = words * sizeof(double);
+  bool ok = need <= C.rec.n ||
+            C.rec.ensure(std::min(S.column_reuse, need + need / 16)) == hipSuccess;
+  ok = ok && C.info.ensure((size_t)C.cols * sizeof(int2)) == hipSuccess;
+  ok = ok && C.sx.ensure(C.nxy * 4) == hipSuccess && C.sy.ensure(C.nxy * 4) == hipSuccess;
+  ok = ok && C.flag.ensure(sizeof(int)) == hipSuccess && C.hflag.ensure(64) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    C.release();
+    return CWBL_OK;
+  }
+  HIPCHK(launch_coord_snapshot(S.stream, true, v.sd.x, C.sx.as<float>(), (long long)C.nxy, nullptr));
+  HIPCHK(launch_coord_snapshot(S.stream, true, v.sd.y, C.sy.as<float>(), (long long)C.nxy, nullptr));
+  v.reuse = 1;
+  v.ncached = (long long)C.off.size();
+  return CWBL_OK;
+}
+
 // ---- CWBL_OPT_COLUMN_SHARE ---------------------------------------------------------------------
 // Why a call of one variable does not run once per column, from what is known before the
 // trees are planned (CWBL_COLUMN_SHARED: it may).  The type rule restates build_family's
@@ -1846,7 +2001,8 @@ int solve_batch_path(VarCall &v, long long g0, int nb, const int *ncnt, const in
 int column_reason(const VarCall &v) {
   if (!S.column_share) return CWBL_COLUMN_REASON_OFF;
   if (v.nvar > 1) return CWBL_COLUMN_REASON_GROUP;
-  if (v.sl->nz < 2) return CWBL_COLUMN_REASON_NZ;
+  // (where the column cache serves, a call of one level is shared too: it fills or hits)
+  if (v.sl->nz < (column_reuse_path() ? 1 : 2)) return CWBL_COLUMN_REASON_NZ;
   if (!(record_path() || wave_path() || handoff_path())) return CWBL_COLUMN_REASON_PATH;
   for (const ObsType &ot : S.obs) {
     if (ot.nobs <= 0 || (ot.family == 0 && !is_gts_assimilated(ot.type_id))) continue;
@@ -1906,8 +2062,12 @@ int factor_levels_per_wave(int ncol, int nl) {
 // workspace of the call; one launch of the level kernel then solves the levels 1 .. nz-1 of
 // every column from them.  The record cache is not involved.  done = false (and nothing
 // launched) when the workspace cannot be allocated: the caller runs the chunks, no error.
+// crec: a cached batch's region of the column cache (CWBL_OPT_COLUMN_REUSE), the factors' place
+// instead of S.wsf, sub-batch s0 starting s0 factors in.  A fill (hit false) runs as above; a hit
+// runs no hand-off kernel and no fill, and one launch of the all-levels kernel per (sub-)batch
+// solves the levels 0 .. nz-1 from the kept factors.
 int solve_batch_column_factor(VarCall &v, long long g0, int nb, const int *ncnt, const int *nidx,
-                              int2 *infob, bool &done) {
+                              int2 *infob, bool &done, double *crec = nullptr, bool hit = false) {
   const TreeDesc *dtrees = S.tdesc.as<TreeDesc>();
   const SolveConsts &c = v.c;
   const int nz = v.nlev, nt = v.nt, list_cap = v.list_cap;
@@ -1921,20 +2081,35 @@ int solve_batch_column_factor(VarCall &v, long long g0, int nb, const int *ncnt,
     Bs = sub_batch(nb, std::min<long long>(S.big_sub, fit));
   }
   // (+1: the spare entry, as the record cache's regions have one)
-  if (S.wsf.ensure((size_t)(std::min<long long>(Bs, nb) + 1) * fwords * 8) != hipSuccess) {
+  if (!crec &&
+      S.wsf.ensure((size_t)(std::min<long long>(Bs, nb) + 1) * fwords * 8) != hipSuccess) {
     (void)hipGetLastError();
     CI.from_factor = 0;
     CI.levels_per_wave = 0;
     done = false;
     return CWBL_OK;
   }
-  if (handoff) HIPCHK(S.wsa.ensure((size_t)Bs * rec_bytes));
-  double *const fac = S.wsf.as<double>();
+  if (handoff && !hit) HIPCHK(S.wsa.ensure((size_t)Bs * rec_bytes));
   int kt;
   for (long long s0 = 0; s0 < nb; s0 += Bs) {
     const int ns = (int)std::min<long long>(Bs, nb - s0);
     int2 *const inf = infob + s0;
+    double *const fac = crec ? crec + (size_t)s0 * fwords : S.wsf.as<double>();
     HIPCHK(kt_begin(S.stream, &kt));
+    if (hit) {
+      const int lw = factor_levels_per_wave(ns, nz);
+      CI.levels_per_wave = lw;
+      if (handoff)
+        HIPCHK(launch_solve_tqb_factor_column_all(S.stream, S.kp, c, v.full, g0 + s0, ns, nz, lw,
+                                                  fac, inf));
+      else
+        HIPCHK(launch_solve_tq_wave_factor_column_all(S.stream, S.kp, c, v.full, g0 + s0, ns, nz,
+                                                      lw, fac, inf));
+      HIPCHK(kt_end(S.stream, kt,
+                    handoff ? KT_SOLVE_TQB_FACTOR_COLUMN_ALL : KT_SOLVE_TQ_WAVE_FACTOR_COLUMN_ALL,
+                    (long long)ns * nz));
+      continue;
+    }
     if (handoff) {
       HIPCHK(launch_big_handoff(S.stream, S.kp, dtrees, c, v.sd, g0 + s0, ns, ncnt + s0 * nt,
                                 nidx + s0 * list_cap, inf, S.wsa.as<double>()));
@@ -1947,6 +2122,10 @@ int solve_batch_column_factor(VarCall &v, long long g0, int nb, const int *ncnt,
       HIPCHK(launch_fill_tq_wave(S.stream, S.kp, dtrees, c, v.sd, g0 + s0, ns, ncnt + s0 * nt,
                                  nidx + s0 * list_cap, inf, fac));
       HIPCHK(kt_end(S.stream, kt, KT_FILL_TQ_WAVE, ns));
+    }
+    if (nz < 2) {  // (a call of one level, CWBL_OPT_COLUMN_REUSE: the fill was all of it)
+      CI.levels_per_wave = 0;
+      continue;
     }
     const int lw = factor_levels_per_wave(ns, nz - 1);
     CI.levels_per_wave = lw;
@@ -1979,8 +2158,13 @@ int solve_batch_column_factor(VarCall &v, long long g0, int nb, const int *ncnt,
 //                           every level; a remainder of one level runs the single kernel with
 //                           sd.var offset likewise.  The batch's lists, and on the record path
 //                           its records, serve every chunk.
+// crec / hit: a cached batch's region of the column cache (CWBL_OPT_COLUMN_REUSE).  Such a batch
+// always runs the one-factor form, whatever the two options say: on the record path the
+// assembly straight into the region and solve_tq40_column_kernel, a hit the latter alone; above
+// k = 40 solve_batch_column_factor on the region.
 int solve_batch_column(VarCall &v, long long g0, int nb, const int *ncnt, const int *nidx,
-                       int2 *infob, hipEvent_t b2, hipEvent_t dn) {
+                       int2 *infob, hipEvent_t b2, hipEvent_t dn, double *crec = nullptr,
+                       bool hit = false) {
   const int nz = v.nlev;
   const long long nxy = (long long)v.full.nx * v.full.ny;
   float *const var0 = v.full.var;
@@ -2013,12 +2197,14 @@ int solve_batch_column(VarCall &v, long long g0, int nb, const int *ncnt, const 
       v.lev = 1;
     }
   } restore{v, v.tv, v.sd, v.group};
-  if (column_factor_path()) {
+  if (column_factor_path() || (crec && !record_path())) {
     bool done = false;
-    if (int rc = solve_batch_column_factor(v, g0, nb, ncnt, nidx, infob, done)) return rc;
+    if (int rc = solve_batch_column_factor(v, g0, nb, ncnt, nidx, infob, done, crec, hit))
+      return rc;
     if (done) return CWBL_OK;  // (else: no workspace, the chunks below)
   }
-  CI.chunk_launches = v.colshare == 1 && record_path() ? 0 : (nz + kMaxGroupVars - 1) / kMaxGroupVars;
+  const bool column_kernel = v.colshare == 1 || crec;
+  CI.chunk_launches = column_kernel && record_path() ? 0 : (nz + kMaxGroupVars - 1) / kMaxGroupVars;
   if (!record_path()) {
     for (int kz0 = 0; kz0 < nz; kz0 += kMaxGroupVars) {
       chunk(kz0, std::min(kMaxGroupVars, nz - kz0));
@@ -2028,17 +2214,21 @@ int solve_batch_column(VarCall &v, long long g0, int nb, const int *ncnt, const 
   }
   const TreeDesc *dtrees = S.tdesc.as<TreeDesc>();
   const long long Bs = record_sub_batch(nb);
-  HIPCHK(S.wsa.ensure((size_t)(Bs + 1) * 8 * AsmRecord<kTq4KP>::WORDS));
-  double *const rec = S.wsa.as<double>();
+  if (!crec) HIPCHK(S.wsa.ensure((size_t)(Bs + 1) * 8 * AsmRecord<kTq4KP>::WORDS));
+  // a cached batch keeps every sub-batch's records, S.wsa only the current one's
+  const size_t rstep = crec ? AsmRecord<kTq4KP>::WORDS : 0;
   int kt;
   for (long long s0 = 0; s0 < nb; s0 += Bs) {
     const int ns = (int)std::min<long long>(Bs, nb - s0);
     int2 *const inf = infob + s0;
-    HIPCHK(kt_begin(S.stream, &kt));
-    HIPCHK(launch_assemble_record(S.stream, S.kp, dtrees, v.c, restore.sd, g0 + s0, ns,
-                                  ncnt + s0 * v.nt, nidx + s0 * v.list_cap, inf, rec));
-    HIPCHK(kt_end(S.stream, kt, KT_ASSEMBLE_RECORD, ns));
-    if (v.colshare == 1) {
+    double *const rec = crec ? crec + (size_t)s0 * rstep : S.wsa.as<double>();
+    if (!hit) {
+      HIPCHK(kt_begin(S.stream, &kt));
+      HIPCHK(launch_assemble_record(S.stream, S.kp, dtrees, v.c, restore.sd, g0 + s0, ns,
+                                    ncnt + s0 * v.nt, nidx + s0 * v.list_cap, inf, rec));
+      HIPCHK(kt_end(S.stream, kt, KT_ASSEMBLE_RECORD, ns));
+    }
+    if (column_kernel) {
       const int lw = column_levels_per_wave(ns, nz);
       CI.levels_per_wave = lw;
       HIPCHK(kt_begin(S.stream, &kt));
@@ -2120,7 +2310,9 @@ int finish_call(VarCall &v, cwbl_stats &st) {
   st.nobs_sum = (long long)ds.nobs_sum * lev;
   // (a hit ran none, or only the uncached batches', of the searches that count this: the
   // inputs being equal, the fill's total holds)
-  st.lz_truncated = v.reuse == 2 ? S.cache.lz_truncated : (long long)ds.lz_truncated * lev;
+  st.lz_truncated = v.reuse != 2   ? (long long)ds.lz_truncated * lev
+                    : v.colcache ? S.ccache.lz_truncated * lev
+                                 : S.cache.lz_truncated;
   st.nonconverged = (long long)ds.nonconverged * lev;
   st.sweeps_sum = (long long)ds.sweeps_sum * lev;
   st.max_p = (int)ds.max_p;
@@ -2219,6 +2411,7 @@ int cwbl_init(const cwbl_init_params *p) {
   S.column_share = 0;
   S.column_levels = 0;
   S.column_factor = false;
+  S.column_reuse = 0;
   S.factor_reuse = true;
   S.hit_merge = true;
   S.wave_reuse = false;
@@ -2228,6 +2421,7 @@ int cwbl_init(const cwbl_init_params *p) {
   S.ncu = prop.multiProcessorCount;
   std::memset(&P, 0, sizeof P);
   std::memset(&CI, 0, sizeof CI);
+  std::memset(&CR, 0, sizeof CR);
   std::memset(&TI, 0, sizeof TI);
   S.lead_div = 0;
   S.serial_search = false;
@@ -2262,6 +2456,15 @@ int cwbl_set_option(int option, long long value) {
       return CWBL_OK;
     }
     (option == CWBL_OPT_HIT_MERGE ? S.hit_merge : S.host_pipe) = value == 1;
+    return CWBL_OK;
+  }
+  if (option == CWBL_OPT_COLUMN_LEVELS) {
+    // how many levels a wavefront of a column or level kernel takes: neither cache keeps
+    // anything that depends on it, and a column cache's hit may be split otherwise than its fill
+    if (!range(0, 1 << 30))
+      return fail(CWBL_ERR_ARG, "cwbl_set_option: value %lld out of range for option %d", value,
+                  option);
+    S.column_levels = (int)value;
     return CWBL_OK;
   }
   ++S.gen;  // options change the neighbour order and the batch plan: kept records are void
@@ -2323,10 +2526,6 @@ int cwbl_set_option(int option, long long value) {
       if (!range(0, 2)) break;
       S.column_share = (int)value;
       return CWBL_OK;
-    case CWBL_OPT_COLUMN_LEVELS:
-      if (!range(0, 1 << 30)) break;
-      S.column_levels = (int)value;
-      return CWBL_OK;
     case CWBL_OPT_RECORD_REUSE:
       if (!range(0, 1LL << 24)) break;
       S.reuse_budget = (size_t)value << 20;
@@ -2350,6 +2549,12 @@ int cwbl_set_option(int option, long long value) {
       if (!range(0, 1)) break;
       S.rows_reuse = value == 1;
       if (S.cache.form == CacheForm::BigFactor) S.cache.release();  // off holds no memory
+      return CWBL_OK;
+    case CWBL_OPT_COLUMN_REUSE:
+      if (!range(0, 1LL << 24)) break;
+      S.column_reuse = (size_t)value << 20;
+      (void)hipStreamSynchronize(S.stream);
+      S.ccache.release();  // 0 holds no memory; the next fill allocates within the new budget
       return CWBL_OK;
     default:
       return fail(CWBL_ERR_ARG, "cwbl_set_option: unknown option %d", option);
@@ -2403,6 +2608,13 @@ int cwbl_column_info(cwbl_column_info_t *out) {
   if (int rc = require_device()) return rc;
   if (!out) return fail(CWBL_ERR_ARG, "cwbl_column_info: null argument");
   *out = CI;
+  return CWBL_OK;
+}
+
+int cwbl_column_reuse_info(cwbl_column_reuse_info_t *out) {
+  if (int rc = require_device()) return rc;
+  if (!out) return fail(CWBL_ERR_ARG, "cwbl_column_reuse_info: null argument");
+  *out = CR;
   return CWBL_OK;
 }
 
@@ -2510,6 +2722,7 @@ static int begin_call(const cwbl_slab *sl) {
   std::memset(&P, 0, sizeof P);
   std::memset(&R, 0, sizeof R);
   std::memset(&CI, 0, sizeof CI);
+  std::memset(&CR, 0, sizeof CR);
   std::memset(&TI, 0, sizeof TI);
   g_pspans.clear();
   g_pev_used = 0;
@@ -2594,8 +2807,14 @@ static int analyze_call(VarCall &v, cwbl_stats *stats) {
   const long long npts = (long long)sl->ix_lim * sl->iy_lim * sl->nz;
   st.points = v.npts = npts;
   RecordCache &C = S.cache;
+  ColumnCache &CC = S.ccache;
   auto finish = [&]() {
     R.bytes_held = (long long)C.bytes();
+    CR.bytes_held = (long long)CC.bytes();
+    CR.form = CC.form == CacheForm::Records      ? CWBL_COLUMN_FORM_RECORDS
+              : CC.form == CacheForm::WaveFactor ? CWBL_COLUMN_FORM_WAVE
+              : CC.form == CacheForm::BigFactor  ? CWBL_COLUMN_FORM_BIG
+                                                 : CWBL_COLUMN_FORM_NONE;
     st.ms_total =
         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
     if (stats) *stats = st;
@@ -2643,9 +2862,31 @@ static int analyze_call(VarCall &v, cwbl_stats *stats) {
     }
     if (v.reuse != 2) C.valid = false;
   }
+  // The column cache (CWBL_OPT_COLUMN_REUSE): a candidate for sharing on a path the option serves.
+  // An equal key means the fill's trees were confirmed 2-D under the same obs set, options and
+  // type parameters, so the slab is staged as a shared call's before the trees are planned.
+  const bool creuse_on = col_candidate && !v.group && column_reuse_path() && npts > 0;
+  ColumnKey ckey;
+  if (creuse_on) {
+    make_column_key(ckey, vp, sl);
+    v.colcache = true;
+    if (CC.valid && std::memcmp(&ckey, &CC.key, sizeof ckey) == 0) {
+      v.colshare = S.column_share;
+      if (int rc = stage_slab(v)) return rc;
+      staged = true;
+      bool same = false;
+      if (int rc = column_coords_match(v, same)) return rc;
+      if (same) {
+        v.reuse = 2;
+        v.ncached = (long long)CC.off.size();
+        v.full_hit = CC.off.size() == CC.plan.size();
+      }
+    }
+    if (v.reuse != 2) CC.valid = false;
+  }
   if (v.full_hit) {
-    v.nt = C.nt;
-    v.list_cap = C.list_cap;
+    v.nt = v.colcache ? CC.nt : C.nt;
+    v.list_cap = v.colcache ? CC.list_cap : C.list_cap;
   } else if (int rc = plan_trees(v)) {
     return rc;
   }
@@ -2657,7 +2898,7 @@ static int analyze_call(VarCall &v, cwbl_stats *stats) {
     return finish();
   }
   for (const TreeDesc &d : v.descs) st.q1_undefined += d.q1_undef ? npts : 0;
-  if (v.full_hit) st.q1_undefined = C.q1_undefined;
+  if (v.full_hit) st.q1_undefined = v.colcache ? 0 : C.q1_undefined;  // (shared: never Q1)
   // The planned trees decide whether the call is shared per column, and name the Q1 case.  (A
   // candidate with a tree that is not 2-D would mean column_reason and build_family disagree:
   // it runs per point like any other call that is not eligible, with its record reuse off.)
@@ -2667,7 +2908,12 @@ static int analyze_call(VarCall &v, cwbl_stats *stats) {
     if ((CI.reason == CWBL_COLUMN_SHARED || CI.reason == CWBL_COLUMN_REASON_3D) && d.q1_undef)
       CI.reason = CWBL_COLUMN_REASON_Q1;
   }
-  if (CI.reason == CWBL_COLUMN_SHARED) v.colshare = S.column_share;
+  v.colshare = CI.reason == CWBL_COLUMN_SHARED ? S.column_share : 0;
+  if (!v.colshare && v.colcache) {  // not shared after all: per point, and no column cache
+    v.colcache = false;
+    v.reuse = 0;
+    v.ncached = 0;
+  }
   HIPCHK(event(1, &e1));
   HIPCHK(hipEventRecord(e1, S.stream));
   HIPCHK(event(2, &e2));
@@ -2684,12 +2930,28 @@ static int analyze_call(VarCall &v, cwbl_stats *stats) {
     CI.levels = v.nlev;
   }
   plan_batches(v);
-  if (v.reuse == 2 && v.plan != C.plan)
+  if (v.reuse == 2 && !v.colcache && v.plan != C.plan)
     return fail(CWBL_ERR_STATE, "record reuse: the batch plan changed under an equal key");
+  if (v.reuse == 2 && v.colcache && v.plan != CC.plan) {
+    // another batch plan under an equal key: a miss.  (A full hit planned no trees yet; the
+    // plan follows their list capacity.)
+    v.reuse = 0;
+    v.ncached = 0;
+    CC.valid = false;
+    if (v.full_hit) {
+      v.full_hit = false;
+      if (int rc = plan_trees(v)) return rc;
+      st.ntrees = v.nt;
+      v.plan.clear();
+      plan_batches(v);
+    }
+  }
   if (int rc = stage_bounce(v)) return rc;
   if (int rc = alloc_call_buffers(v)) return rc;
   if (reuse_on && v.reuse != 2)
     if (int rc = begin_fill(v, key, form)) return rc;
+  if (v.colcache && v.reuse != 2)
+    if (int rc = begin_column_fill(v, ckey)) return rc;
   if (int rc = plan_hit_merge(v, form)) return rc;
   if (int rc = restore_info(v, 0)) return rc;
   HIPCHK(event(3, &e_ready));  // inputs staged and the counters cleared
@@ -2725,9 +2987,12 @@ static int analyze_call(VarCall &v, cwbl_stats *stats) {
     HIPCHK(event(ev + 2, &b2));
     HIPCHK(event(ev + 3, &dn));
     // a cached batch: its region of the record cache; on a hit neither lists nor assembly
-    double *const crec = bi < v.ncached ? C.rec.as<double>() + C.off[bi] : nullptr;
-    const size_t aoff = crec ? C.off[bi] / C.words() * FactorAux<kTq4KP>::WORDS : 0;
-    double *const caux = crec && form_has_aux(form) ? C.aux.as<double>() + aoff : nullptr;
+    double *const crec = bi >= v.ncached ? nullptr
+                         : v.colcache    ? CC.rec.as<double>() + CC.off[bi]
+                                         : C.rec.as<double>() + C.off[bi];
+    const bool has_aux = crec && !v.colcache && form_has_aux(form);
+    const size_t aoff = has_aux ? C.off[bi] / C.words() * FactorAux<kTq4KP>::WORDS : 0;
+    double *const caux = has_aux ? C.aux.as<double>() + aoff : nullptr;
     const bool hit = crec && v.reuse == 2;
     if (hit && v.merge) {
       // the cached batches of this window: [bi, be)
@@ -2760,7 +3025,7 @@ static int analyze_call(VarCall &v, cwbl_stats *stats) {
       if (int rc = upload_batch_var(v, bi)) return rc;
     HIPCHK(hipEventRecord(b2, S.stream));
     if (v.colshare) {
-      if (int rc = solve_batch_column(v, g0, nb, ncnt, nidx, infob, b2, dn)) return rc;
+      if (int rc = solve_batch_column(v, g0, nb, ncnt, nidx, infob, b2, dn, crec, hit)) return rc;
     } else if (int rc = solve_batch_path(v, g0, nb, ncnt, nidx, infob, b2, dn, crec,
                                        crec ? form : CacheForm::None, hit, caux)) {
       return rc;
@@ -2787,14 +3052,25 @@ static int analyze_call(VarCall &v, cwbl_stats *stats) {
     v.ev += v.tune_batch ? 5 : 4;
   }
   if (int rc = finish_call(v, st)) return rc;
-  if (v.reuse == 1) {  // the fill is complete: the next call may solve from it
+  if (v.colcache) {  // the column cache's fill is complete, or its hit is reported
+    if (v.reuse == 1) {
+      CC.nt = v.nt;
+      CC.list_cap = v.list_cap;
+      CC.lz_truncated = st.lz_truncated / std::max(v.nlev, 1);
+      CC.valid = true;
+      CR.columns_filled = CC.cols;
+    } else if (v.reuse == 2) {
+      CR.columns_reused = CC.cols;
+      CR.batches_reused = v.ncached;
+    }
+  } else if (v.reuse == 1) {  // the fill is complete: the next call may solve from it
     C.nt = v.nt;
     C.list_cap = v.list_cap;
     C.lz_truncated = st.lz_truncated;
     C.q1_undefined = st.q1_undefined;
     C.valid = true;
   }
-  R.batches_reused = v.reuse == 2 ? v.ncached : 0;
+  R.batches_reused = v.reuse == 2 && !v.colcache ? v.ncached : 0;  // (the record cache's)
   R.batches_assembled = nbat - R.batches_reused;
   return finish();
 }

@@ -520,6 +520,18 @@ hipError_t launch_solve_tqb_factor_column(hipStream_t s, int kp, SolveConsts c, 
                                           long long g0, int ncol, int nz, int lw,
                                           const double *fac, const int2 *info);
 
+// A column-shared call that hits the column cache (CWBL_OPT_COLUMN_REUSE): the two kernels above
+// started at level 0, since no fill of this call analysed it.  `fac` and info[i].x are what an
+// earlier call's fill left for the ncol columns from g0; these solve the levels 0 .. nz-1 of
+// every column (grid (ncol, ceil(nz / lw))).  cwbl_tq_wave_column_all.hip (KP = 48, 56, 64) and
+// cwbl_tq_big_column_all.hip (KP = 96).
+hipError_t launch_solve_tq_wave_factor_column_all(hipStream_t s, int kp, SolveConsts c,
+                                                  SlabDev slab, long long g0, int ncol, int nz,
+                                                  int lw, const double *fac, const int2 *info);
+hipError_t launch_solve_tqb_factor_column_all(hipStream_t s, int kp, SolveConsts c, SlabDev slab,
+                                              long long g0, int ncol, int nz, int lw,
+                                              const double *fac, const int2 *info);
+
 // KP = 96, 128: one 256-thread workgroup per point (cwbl_tq_big.hip)
 hipError_t launch_solve_tq_big(hipStream_t s, int kp, bool assembled, const TreeDesc *trees,
                                SolveConsts c, SlabDev slab, long long g0, int npts,

@@ -395,6 +395,44 @@ __device__ __forceinline__ void tqb_factor_hit(TailSmem<KP, J0> &sm, const Solve
       });
 }
 
+// The body of a level kernel of a column-shared call, with the first level as an argument: the
+// levels kzf + lw blockIdx.y .. of column blockIdx.x (through xcd_remap_rev) from the
+// BigFactor<KP, J0> at fac + gi WORDS, each one tqb_factor_hit at the level's var index.
+// cwbl_tq_big_column_all.hip calls it with kzf = 0 (every level of a column whose factor the
+// column cache kept, CWBL_OPT_COLUMN_REUSE).  It is the text of solve_tqb_factor_column_kernel
+// (cwbl_tq_big_column.hip), which starts at level 1 and keeps its own copy: as a caller of this
+// function that kernel compiles to another schedule (profiles/column_reuse.txt), and its assembly
+// is not to change.  sm is the workgroup's own; info is read only.
+template <int KP, int J0>
+__device__ __forceinline__ void tqb_factor_levels(TailSmem<KP, J0> &sm, const SolveConsts &c,
+                                                  const SlabDev &slab, long long g0, int ncol,
+                                                  int nz, int lw, int kzf,
+                                                  const double *__restrict__ fac,
+                                                  const int2 *__restrict__ info) {
+  const int gi = xcd_remap_rev(blockIdx.x, gridDim.x);  // the tail's XCD-chunk order
+  if (gi >= ncol) return;
+  const int kz0 = kzf + (int)blockIdx.y * lw, kz1 = min(nz, kz0 + lw);  // levels [kz0, kz1)
+  if (kz0 >= kz1) return;
+  const int l = threadIdx.x;
+  const int k = c.k;
+  const int ptot = info[gi].x;
+  if (ptot == 0) return;  // no accepted observation: var stays as it is at every level
+
+  // the column's point at level 0 (g0 + gi < ix_lim iy_lim); level kz lies nx ny kz further
+  const long long P0 = bf_point_index(slab, g0 + gi);
+  const long long nxy = (long long)slab.nx * slab.ny;
+  for (int kz = kz0; kz < kz1; ++kz) {
+    // the previous level has read sm (one wavefront: the barrier orders the LDS accesses)
+    if (kz != kz0) __syncthreads();
+    // redefined per level: the factor's address, and the lane, which the masks, the lane offsets
+    // and the LDS addresses of a level derive from
+    const double *fp = fac;
+    int ll = l;
+    asm volatile("" : "+s"(fp), "+v"(ll));
+    tqb_factor_hit<KP, J0, false>(sm, c, slab, gi, ll, k, P0 + nxy * kz, fp, ptot, nullptr);
+  }
+}
+
 }  // namespace
 
 // solve_tqb_tail_kernel<KP, J0, 2> (see there for the step's derivation) with the factor's

@@ -31,7 +31,7 @@ OPT_BIG_PATH, OPT_BIG_BATCH, OPT_PAGEABLE, OPT_BIN_DIV, OPT_LEAD_DIV, OPT_MAX_BA
 OPT_INFO_WINDOW, OPT_INDEX, OPT_RECORD_REUSE = 12, 13, 14
 OPT_COLUMN_SHARE, OPT_COLUMN_LEVELS, OPT_FACTOR_REUSE, OPT_HIT_MERGE = 15, 16, 17, 18
 OPT_WAVE_REUSE, OPT_HOST_PIPE, OPT_BIG_REUSE, OPT_ROWS_REUSE = 19, 20, 21, 22
-OPT_COLUMN_FACTOR = 23
+OPT_COLUMN_FACTOR, OPT_COLUMN_REUSE = 23, 24
 OPTIONS = {"solver": OPT_SOLVER, "split40": OPT_SPLIT40, "split40_batch": OPT_SPLIT40_BATCH,
            "search": OPT_SEARCH,
            "big_path": OPT_BIG_PATH, "big_batch": OPT_BIG_BATCH, "pageable": OPT_PAGEABLE,
@@ -41,11 +41,15 @@ OPTIONS = {"solver": OPT_SOLVER, "split40": OPT_SPLIT40, "split40_batch": OPT_SP
            "column_levels": OPT_COLUMN_LEVELS, "factor_reuse": OPT_FACTOR_REUSE,
            "hit_merge": OPT_HIT_MERGE, "wave_reuse": OPT_WAVE_REUSE,
            "host_pipe": OPT_HOST_PIPE, "big_reuse": OPT_BIG_REUSE,
-           "rows_reuse": OPT_ROWS_REUSE, "column_factor": OPT_COLUMN_FACTOR}
+           "rows_reuse": OPT_ROWS_REUSE, "column_factor": OPT_COLUMN_FACTOR,
+           "column_reuse": OPT_COLUMN_REUSE}
 
 #: cwbl_column_info_t.reason
 (COLUMN_SHARED, COLUMN_REASON_OFF, COLUMN_REASON_3D, COLUMN_REASON_Q1, COLUMN_REASON_NZ,
  COLUMN_REASON_PATH, COLUMN_REASON_GROUP, COLUMN_REASON_NO_TREES) = range(8)
+
+#: cwbl_column_reuse_info_t.form
+COLUMN_FORM_NONE, COLUMN_FORM_RECORDS, COLUMN_FORM_WAVE, COLUMN_FORM_BIG = range(4)
 
 #: cwbl_transfer_info_t.reason
 (TRANSFER_PIPED, TRANSFER_REASON_OFF, TRANSFER_REASON_REGION, TRANSFER_REASON_REGISTER,
@@ -145,6 +149,15 @@ class ColumnInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class ColumnReuseInfo(C.Structure):
+    _fields_ = [("columns_reused", C.c_longlong), ("columns_filled", C.c_longlong),
+                ("batches_reused", C.c_longlong), ("bytes_held", C.c_longlong),
+                ("ms_compare", C.c_double), ("form", C.c_int), ("reserved", C.c_int)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
 class TransferInfo(C.Structure):
     _fields_ = [("host", C.c_int), ("piped", C.c_int), ("piped_back", C.c_int),
                 ("registered", C.c_int), ("bounce", C.c_int), ("reason", C.c_int),
@@ -162,8 +175,8 @@ EXPORTS = ["cwbl_init", "cwbl_set_stream", "cwbl_set_obs", "cwbl_analyze_var", "
            "cwbl_pack_columns", "cwbl_unpack_columns", "cwbl_pack_members",
            "cwbl_unpack_members", "cwbl_vcoord_mean", "cwbl_member_sum", "cwbl_scale", "cwbl_set_kernel_timing", "cwbl_kernel_times",
            "cwbl_set_option", "cwbl_bin_index", "cwbl_prep_info", "cwbl_reuse_info",
-           "cwbl_column_info", "cwbl_transfer_info", "cwbl_finalize", "cwbl_last_error",
-           "cwbl_abi_version"]
+           "cwbl_column_info", "cwbl_column_reuse_info", "cwbl_transfer_info", "cwbl_finalize",
+           "cwbl_last_error", "cwbl_abi_version"]
 
 
 def _ptr(a):
@@ -350,6 +363,11 @@ def load_library(path=None):
     lib.cwbl_reuse_info.argtypes = [C.POINTER(ReuseInfo)]
     lib.cwbl_column_info.argtypes = [C.POINTER(ColumnInfo)]
     lib.cwbl_transfer_info.argtypes = [C.POINTER(TransferInfo)]
+    # (a library from before the column cache, loaded through CWBL_LIBRARY for an A/B, has none:
+    # Core.column_reuse_info then raises)
+    if hasattr(lib, "cwbl_column_reuse_info"):
+        lib.cwbl_column_reuse_info.argtypes = [C.POINTER(ColumnReuseInfo)]
+        lib.cwbl_column_reuse_info.restype = C.c_int
     lib.cwbl_finalize.argtypes = []
     lib.cwbl_last_error.restype = cp
     lib.cwbl_abi_version.restype = C.c_int
@@ -497,6 +515,15 @@ class Core:
         "column_share" option, and if not why (ColumnInfo; reason: COLUMN_REASON_*)."""
         info = ColumnInfo()
         self._check(self.lib.cwbl_column_info(C.byref(info)))
+        return info
+
+    def column_reuse_info(self):
+        """cwbl_column_reuse_info: what the last analyze_var took from or left in the column
+        cache of the "column_reuse" option (ColumnReuseInfo; form: COLUMN_FORM_*)."""
+        if not hasattr(self.lib, "cwbl_column_reuse_info"):
+            raise CwblError("the loaded library has no cwbl_column_reuse_info")
+        info = ColumnReuseInfo()
+        self._check(self.lib.cwbl_column_reuse_info(C.byref(info)))
         return info
 
     def transfer_info(self):

@@ -95,6 +95,15 @@ module letkf_core_gpu
     ! cwbl_set_option: a column-shared call at k = 41..96 solves every level from one kept factor
     ! per column (1; 0, default: the levels run as group launches of eight)
     integer(c_int), parameter, public :: CWBL_OPT_COLUMN_FACTOR = 23
+    ! cwbl_set_option: MiB of device memory in which a column-shared call keeps each column's
+    ! record (k = 17..40) or factor (k = 41..96) for the next call with the same localisation, x
+    ! and y, whatever its nz (0, default: off; MU, P and PH then pay one search and reduction)
+    integer(c_int), parameter, public :: CWBL_OPT_COLUMN_REUSE = 24
+    ! cwbl_column_reuse_info_t%form
+    integer(c_int), parameter, public :: CWBL_COLUMN_FORM_NONE = 0
+    integer(c_int), parameter, public :: CWBL_COLUMN_FORM_RECORDS = 1
+    integer(c_int), parameter, public :: CWBL_COLUMN_FORM_WAVE = 2
+    integer(c_int), parameter, public :: CWBL_COLUMN_FORM_BIG = 3
     ! cwbl_set_option: host-memory slabs of group calls, column-shared calls and calls with
     ! tune_q = 1 travel batch by batch under the solves (1; 0, default: whole, around them)
     integer(c_int), parameter, public :: CWBL_OPT_HOST_PIPE = 20
@@ -126,6 +135,12 @@ module letkf_core_gpu
         integer(c_int)       :: levels, levels_per_wave, chunk_launches, from_factor
     end type cwbl_column_info_t
 
+    type, bind(C), public :: cwbl_column_reuse_info_t  ! cwbl_column_reuse_info
+        integer(c_long_long) :: columns_reused, columns_filled, batches_reused, bytes_held
+        real(c_double)       :: ms_compare
+        integer(c_int)       :: form, reserved
+    end type cwbl_column_reuse_info_t
+
     type, bind(C), public :: cwbl_transfer_info_t  ! cwbl_transfer_info
         integer(c_int)       :: host, piped, piped_back, registered, bounce, reason
         integer(c_long_long) :: tune_q_launches, bytes_piped_up, bytes_piped_down
@@ -146,7 +161,7 @@ module letkf_core_gpu
               cwbl_vcoord_mean, &
               cwbl_member_sum, cwbl_scale, cwbl_set_stream, cwbl_set_option, &
               cwbl_bin_index, cwbl_prep_info, cwbl_reuse_info, cwbl_column_info, &
-              cwbl_transfer_info, &
+              cwbl_column_reuse_info, cwbl_transfer_info, &
               cwbl_finalize, cwbl_abi_version, cwbl_error, cwbl_check
     ! host obs ingest (include/cwb_letkf_ingest.h); file names and varname are passed as
     ! trim(name)//c_null_char
@@ -368,6 +383,14 @@ module letkf_core_gpu
             import :: c_int, cwbl_column_info_t
             type(cwbl_column_info_t), intent(out) :: info
         end function cwbl_column_info
+
+        ! what the last cwbl_analyze_var took from or left in the column cache
+        ! (CWBL_OPT_COLUMN_REUSE)
+        integer(c_int) function cwbl_column_reuse_info(info) &
+                bind(C, name='cwbl_column_reuse_info')
+            import :: c_int, cwbl_column_reuse_info_t
+            type(cwbl_column_reuse_info_t), intent(out) :: info
+        end function cwbl_column_reuse_info
 
         ! how the last call moved a host slab's var (CWBL_OPT_HOST_PIPE)
         integer(c_int) function cwbl_transfer_info(info) bind(C, name='cwbl_transfer_info')

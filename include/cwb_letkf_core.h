@@ -466,7 +466,7 @@ enum {
                                 * k <= 96 and under CWBL_OPT_BIG_PATH = 0.  Group calls and
                                 * column-shared calls neither read, fill nor invalidate the
                                 * cache */
-  CWBL_OPT_COLUMN_FACTOR = 23  /* 1: a call that is shared per column (CWBL_OPT_COLUMN_SHARE 1
+  CWBL_OPT_COLUMN_FACTOR = 23, /* 1: a call that is shared per column (CWBL_OPT_COLUMN_SHARE 1
                                 * or 2, eligible as there) on the one-wavefront path at
                                 * k = 41..64 or on the hand-off path at k = 65..96 solves every
                                 * level from one kept factor per column instead of running the
@@ -490,6 +490,44 @@ enum {
                                 * k = 97..128, CWBL_OPT_SOLVER = 1, CWBL_OPT_BIG_PATH = 0, group
                                 * calls and calls that are not shared.  Nothing that is cached
                                 * depends on it: setting it leaves a filled cache valid */
+  CWBL_OPT_COLUMN_REUSE = 24   /* device-memory budget in MiB of the column cache: what a call
+                                * that is shared per column keeps for the next one (0 = off, the
+                                * default; 0 releases what is held; cwbl_init resets it).  The
+                                * weights of such a call depend on the column (i, j) alone, not
+                                * on nz, the levels or alt, so the variables of one localisation
+                                * whose slabs share x and y (MU, P, PH: nz = 1, nz, nz + 1) pay one
+                                * search, assembly and reduction.  Eligible: a call that is shared
+                                * under CWBL_OPT_COLUMN_SHARE 1 or 2 (see cwbl_column_info), and
+                                * with this option on also a call of one variable with nz = 1 that
+                                * meets every other condition there; it runs on the column view
+                                * with one level (cwbl_column_info: shared = 1, levels = 1), bit
+                                * for bit the per-point call.  Kept per column of the leading
+                                * column batches that fit the budget: on the record path
+                                * (k = 17..40) the assembled record (6880 B), on the one-wavefront
+                                * path at k = 41..64 and the hand-off path at k = 65..96 the
+                                * factor A = Q T Q^T that CWBL_OPT_COLUMN_FACTOR's fill leaves
+                                * (KP (KP - 1) / 2 + 5 KP fp64 words at most), with the accepted
+                                * counts and a snapshot of x and y.  Cached batches always run
+                                * the one-factor form, whatever CWBL_OPT_COLUMN_SHARE (1 or 2) and
+                                * CWBL_OPT_COLUMN_FACTOR say; batches beyond the budget run what
+                                * they run without the option.  A later eligible call hits when
+                                * the obs set, the options, KP, multi_infl, the types' parameters,
+                                * nx, ny, ix_lim, iy_lim and the batch plan are equal and x and y
+                                * equal the snapshot bit for bit (nz, alt, RTPP / RTPS, tune_q and
+                                * the memory kind may differ).  A hit runs no obs preparation,
+                                * search, assembly, hand-off kernel or fill for the cached
+                                * batches: one launch per cached (sub-)batch solves all nz levels
+                                * (solve_tq40_column_kernel on the kept records;
+                                * solve_tq_wave_factor_column_all_kernel<KP> or
+                                * solve_tqb_factor_column_all_kernel<96, 32> on the kept factors).
+                                * Bit-identical results and equal counters; cwbl_column_reuse_info
+                                * reports.  Anything else is a miss and refills.  A failed
+                                * allocation is no error: the call runs without the cache.  The
+                                * record cache (CWBL_OPT_RECORD_REUSE) is neither read, filled nor
+                                * invalidated by a column call, and a per-point call never touches
+                                * the column cache.  Accepted and ignored at k <= 16, k = 97..128,
+                                * CWBL_OPT_SPLIT40 = 0, CWBL_OPT_SOLVER = 1, CWBL_OPT_BIG_PATH = 0
+                                * and for group calls */
 };
 int         cwbl_set_option(int option, long long value);
 
@@ -555,7 +593,8 @@ int         cwbl_reuse_info(cwbl_reuse_info_t *out);
  * below the fp32 rounding of the analysis), the low bits of some values differ.  Options 1 and
  * 2 always agree with each other bit for bit, whatever CWBL_OPT_COLUMN_LEVELS.
  *
- * Eligibility.  A call is shared when the option is non-zero, it analyses one variable, nz >= 2, the default
+ * Eligibility.  A call is shared when the option is non-zero, it analyses one variable, nz >= 2
+ * (nz = 1 as well where CWBL_OPT_COLUMN_REUSE is on and applies), the default
  * solver runs on the record, the one-wavefront or the hand-off path, and every tree of the
  * call is 2-D with a 2-D query and outside the Q1 undefined case; the check is made after the
  * trees are planned, before any batch work. */
@@ -564,7 +603,7 @@ enum {
   CWBL_COLUMN_REASON_OFF = 1,     /* the option is 0 */
   CWBL_COLUMN_REASON_3D = 2,      /* a used obs type has vclr > 0 */
   CWBL_COLUMN_REASON_Q1 = 3,      /* a family in the Q1 undefined case (CWBL_Q1_REPLICATE) */
-  CWBL_COLUMN_REASON_NZ = 4,      /* nz < 2 */
+  CWBL_COLUMN_REASON_NZ = 4,      /* nz < 2 (nz < 1 where CWBL_OPT_COLUMN_REUSE applies) */
   CWBL_COLUMN_REASON_PATH = 5,    /* CWBL_OPT_SOLVER = 1, or k > 64 under CWBL_OPT_BIG_PATH = 0 */
   CWBL_COLUMN_REASON_GROUP = 6,   /* cwbl_analyze_vars with two or more variables */
   CWBL_COLUMN_REASON_NO_TREES = 7 /* nothing to assimilate: no tree, no analysis */
@@ -585,6 +624,27 @@ typedef struct cwbl_column_info_t {
                                * (CWBL_OPT_COLUMN_FACTOR) */
 } cwbl_column_info_t;
 int         cwbl_column_info(cwbl_column_info_t *out);
+
+/* What the last cwbl_analyze_var did with the column cache (CWBL_OPT_COLUMN_REUSE).  A call that
+ * is not eligible, or runs with the option off, reports zeros but bytes_held. */
+enum {
+  CWBL_COLUMN_FORM_NONE = 0,     /* nothing kept */
+  CWBL_COLUMN_FORM_RECORDS = 1,  /* AsmRecord<40> per column (k = 17..40) */
+  CWBL_COLUMN_FORM_WAVE = 2,     /* WaveFactor<KP> per column (k = 41..64) */
+  CWBL_COLUMN_FORM_BIG = 3       /* BigFactor<96, 32> per column (k = 65..96) */
+};
+typedef struct cwbl_column_reuse_info_t {
+  long long columns_reused;   /* columns whose levels were solved from what an earlier call kept */
+  long long columns_filled;   /* columns whose record or factor this call left in the cache */
+  long long batches_reused;   /* column batches solved from the cache */
+  long long bytes_held;       /* device memory of the column cache after the call: records or
+                               * factors, accepted counts and the snapshot of x and y */
+  double    ms_compare;       /* host time of the compare of x and y with the snapshot, its
+                               * read-back and synchronisation included (0: the key differed) */
+  int       form;             /* CWBL_COLUMN_FORM_* of what the cache holds after the call */
+  int       reserved;         /* 0 */
+} cwbl_column_reuse_info_t;
+int         cwbl_column_reuse_info(cwbl_column_reuse_info_t *out);
 
 /* How the last cwbl_analyze_var (or cwbl_analyze_vars) moved its slab's var between host and
  * device.  A CWBL_MEM_DEVICE call reports zeros.  The bytes are var's alone (x, y and alt are
