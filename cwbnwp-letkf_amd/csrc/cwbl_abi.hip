@@ -251,58 +251,12 @@ struct KTime { long long launches = 0, points = 0; double ms = 0.0; };
 // a FactorAux entry per record outside the budget, so what is cached does not depend on
 // FACTOR_REUSE.  The cached form and the live options cannot disagree on a hit: the key holds
 // State::gen and KP, and cwbl_set_option bumps gen for every option that call_form reads.
-enum class CacheForm { None, Records, Tq40Factor, WaveFactor, BigFactor };
-size_t form_words(CacheForm f, int kp) {  // fp64 words per cached point
-  return f == CacheForm::WaveFactor  ? wave_factor_words(kp)
-         : f == CacheForm::BigFactor ? big_factor_words(kp)
-                                     : (size_t)AsmRecord<kTq4KP>::WORDS;
-}
-bool form_has_aux(CacheForm f) { return f == CacheForm::Tq40Factor; }  // a FactorAux per point
-struct RecordKey {
-  unsigned long long gen;  // State::gen: obs set, cwbl_init constants, options
-  int kp;                  // the path's KP (the record path: kTq4KP)
-  float multi_infl;        // inflat is on the record's diagonal
-  int dims[7];             // nx, ny, nz, alt_nx, alt_ny, ix_lim, iy_lim
-  cwbl_type_params gts[CWBL_NUM_GTS_TYPES], radar[CWBL_NUM_RADAR_TYPES];
-};
-struct RecordCache {
-  bool valid = false;  // a fill completed: everything below describes it
-  RecordKey key{};
-  // Batch b < off.size() of `plan` (the leading batches that fit the budget) keeps its nb
-  // records and the spare one that solve_tq40_kernel's lanes past a launch read, from word
-  // off[b] of `rec`; sub-batch s0 of it starts s0 records on, its spare being the next
-  // sub-batch's first record.  info: (p, level) of the pts cached points as the fill left
-  // them; a hit restores p.  sx, sy, salt: the coordinates the records were assembled from.
-  // aux (factor reuse only): one FactorAux per record of `rec`, spares included, by the same
-  // ordinal: batch b's entries start at entry off[b] / WORDS, sub-batch s0's s0 entries on.
-  DevBuf rec, aux, info, sx, sy, salt, flag;
-  PinBuf hflag;
-  CacheForm form = CacheForm::None;  // what the allocation last served (begin_fill)
-  size_t words() const { return form_words(form, key.kp); }  // fp64 words of a record
-  std::vector<std::pair<long long, int>> plan;
-  std::vector<size_t> off;
-  long long pts = 0;
-  size_t nxy = 0, nalt = 0;
-  // what a call that skips plan_trees and the searches still reports
-  int nt = 0, list_cap = 0;
-  long long lz_truncated = 0, q1_undefined = 0;
-  size_t bytes() const { return rec.n + aux.n + info.n + sx.n + sy.n + salt.n + flag.n; }
-  void release() {
-    valid = false;
-    form = CacheForm::None;
-    for (DevBuf *b : {&rec, &aux, &info, &sx, &sy, &salt, &flag}) b->release();
-    hflag.release();
-    plan.clear();
-    off.clear();
-    pts = 0;
-  }
-};
-
+//
 // The column cache (CWBL_OPT_COLUMN_REUSE): what a column-shared call keeps per COLUMN of its
 // leading column batches, for the next shared call of the same localisation on the same x and y,
-// whatever its nz, alt and epilogue flags (MU, P, PH).  The record cache above is per point and
-// a column call never touches it; a per-point call never touches this one.
-//   form        path                       a cached column      a fill; a hit
+// whatever its nz, alt and epilogue flags (MU, P, PH).  The record cache is per point and a
+// column call never touches it; a per-point call never touches the column cache.
+//   form        path (column_form)         a cached column      a fill; a hit
 //   Records     k = 17..40                 AsmRecord<40>        assemble_record_kernel into the
 //                                                               region, solve_tq40_column_kernel;
 //                                                               the latter alone
@@ -313,39 +267,65 @@ struct RecordCache {
 //                                                               fill_tqb_tail_kernel and the level
 //                                                               kernel from level 1; the
 //                                                               all-levels kernel
-// The key has no nz, alt_nx or alt_ny: a 2-D tree reads neither the level nor alt.
-struct ColumnKey {
+// Its key holds 0 for nz, alt_nx and alt_ny, and its snapshot no alt: a 2-D tree reads neither
+// the level nor alt.
+//
+// Both are one Cache, filled and read by one text (cache_candidate, cache_coords_match,
+// begin_cache_fill, complete_cache_call); where they differ, per_column (of the call that is
+// bound to one: v.colcache) says so there.
+enum class CacheForm { None, Records, Tq40Factor, WaveFactor, BigFactor };
+size_t form_words(CacheForm f, int kp) {  // fp64 words per cached point
+  return f == CacheForm::WaveFactor  ? wave_factor_words(kp)
+         : f == CacheForm::BigFactor ? big_factor_words(kp)
+                                     : (size_t)AsmRecord<kTq4KP>::WORDS;
+}
+bool form_has_aux(CacheForm f) { return f == CacheForm::Tq40Factor; }  // a FactorAux per point
+int form_column_code(CacheForm f) {  // cwbl_column_reuse_info_t::form
+  return f == CacheForm::Records      ? CWBL_COLUMN_FORM_RECORDS
+         : f == CacheForm::WaveFactor ? CWBL_COLUMN_FORM_WAVE
+         : f == CacheForm::BigFactor  ? CWBL_COLUMN_FORM_BIG
+                                      : CWBL_COLUMN_FORM_NONE;
+}
+struct CacheKey {
   unsigned long long gen;  // State::gen: obs set, cwbl_init constants, options
-  int kp;
-  float multi_infl;
-  int dims[4];             // nx, ny, ix_lim, iy_lim
+  int kp;                  // the path's KP (the record path: kTq4KP)
+  float multi_infl;        // inflat is on the record's diagonal
+  int dims[7];             // nx, ny, nz, alt_nx, alt_ny, ix_lim, iy_lim (per column: nz, alt 0)
   cwbl_type_params gts[CWBL_NUM_GTS_TYPES], radar[CWBL_NUM_RADAR_TYPES];
 };
-struct ColumnCache {
-  bool valid = false;  // a fill completed: everything below describes it
-  ColumnKey key{};
-  // Batch b < off.size() of `plan` keeps its nb entries and a spare one from word off[b] of
-  // `rec`, sub-batch s0 of it s0 entries on (RecordCache's layout).  info: (p, level) of the
-  // `cols` cached columns as the fill left them.  sx, sy: the coordinates of the fill.
-  DevBuf rec, info, sx, sy, flag;
+struct Cache {
+  const bool per_column;  // the column cache: a unit is a column of a shared call, not a point
+  bool valid = false;     // a fill completed: everything below describes it
+  CacheKey key{};
+  // Batch b < off.size() of `plan` (the leading batches that fit the budget) keeps its nb
+  // records and the spare one that solve_tq40_kernel's lanes past a launch read, from word
+  // off[b] of `rec`; sub-batch s0 of it starts s0 records on, its spare being the next
+  // sub-batch's first record.  info: (p, level) of the `units` cached points or columns as the
+  // fill left them; a hit restores p.  sx, sy, salt: the coordinates the records were assembled
+  // from (per column: no alt, nalt = 0).
+  // aux (form Tq40Factor only): one FactorAux per record of `rec`, spares included, by the same
+  // ordinal: batch b's entries start at entry off[b] / WORDS, sub-batch s0's s0 entries on.
+  DevBuf rec, aux, info, sx, sy, salt, flag;
   PinBuf hflag;
-  CacheForm form = CacheForm::None;
+  CacheForm form = CacheForm::None;  // what the allocation last served (begin_cache_fill)
+  size_t words() const { return form_words(form, key.kp); }  // fp64 words of a record
   std::vector<std::pair<long long, int>> plan;
   std::vector<size_t> off;
-  long long cols = 0;
-  size_t nxy = 0;
-  // what a call that skips plan_trees and the searches still reports (lz_truncated: per level)
+  long long units = 0;
+  size_t nxy = 0, nalt = 0;
+  // what a call that skips plan_trees and the searches still reports (lz_truncated: per level
+  // of the filling call, which a per-point call has one of)
   int nt = 0, list_cap = 0;
-  long long lz_truncated = 0;
-  size_t bytes() const { return rec.n + info.n + sx.n + sy.n + flag.n; }
+  long long lz_truncated = 0, q1_undefined = 0;
+  size_t bytes() const { return rec.n + aux.n + info.n + sx.n + sy.n + salt.n + flag.n; }
   void release() {
     valid = false;
     form = CacheForm::None;
-    for (DevBuf *b : {&rec, &info, &sx, &sy, &flag}) b->release();
+    for (DevBuf *b : {&rec, &aux, &info, &sx, &sy, &salt, &flag}) b->release();
     hflag.release();
     plan.clear();
     off.clear();
-    cols = 0;
+    units = 0;
   }
 };
 
@@ -427,8 +407,8 @@ struct State {
                                   // factor per column (k = 41..96)
   int ncu = 0;                    // compute units of the device (automatic level split)
   size_t column_reuse = 0;        // CWBL_OPT_COLUMN_REUSE in bytes (0: off)
-  RecordCache cache;
-  ColumnCache ccache;
+  Cache cache{false};   // the record cache (CWBL_OPT_RECORD_REUSE)
+  Cache ccache{true};   // the column cache (CWBL_OPT_COLUMN_REUSE)
   // pageable host slabs: each batch's var columns go through page-locked bounce slots (two
   // in, two out), filled and drained by a few host threads while the GPU runs other batches
   static constexpr int kSlots = 3;
@@ -1166,8 +1146,9 @@ struct VarCall {
   int reuse = 0;
   long long ncached = 0;
   bool full_hit = false;
-  // the cache that reuse, ncached and full_hit speak of is the column cache
-  // (CWBL_OPT_COLUMN_REUSE: a column-shared call), not the record cache
+  // the cache that reuse, ncached and full_hit speak of (null: the call has none); colcache:
+  // it is the column cache (CWBL_OPT_COLUMN_REUSE: a column-shared call), not the record cache
+  Cache *cache = nullptr;
   bool colcache = false;
   // CWBL_OPT_HIT_MERGE: the call's cached batches go out in one launch per info window;
   // hitseg_used: entries of S.hitseg_pin taken by the launches so far
@@ -1209,22 +1190,26 @@ CacheForm call_form() {
   return CacheForm::None;
 }
 
-void make_record_key(RecordKey &key, const cwbl_var_params *vp, const cwbl_slab *sl) {
+void make_cache_key(CacheKey &key, const cwbl_var_params *vp, const cwbl_slab *sl,
+                    bool per_column) {
   std::memset(&key, 0, sizeof key);
   key.gen = S.gen;
   key.kp = S.kp;
   key.multi_infl = vp->multi_infl;
-  const int dims[7] = {sl->nx, sl->ny, sl->nz, sl->alt_nx, sl->alt_ny, sl->ix_lim, sl->iy_lim};
+  const int dims[7] = {sl->nx, sl->ny, per_column ? 0 : sl->nz, per_column ? 0 : sl->alt_nx,
+                       per_column ? 0 : sl->alt_ny, sl->ix_lim, sl->iy_lim};
   std::memcpy(key.dims, dims, sizeof dims);
   std::memcpy(key.gts, vp->gts, sizeof key.gts);
   std::memcpy(key.radar, vp->radar, sizeof key.radar);
 }
 
+size_t cache_budget(const Cache &C) { return C.per_column ? S.column_reuse : S.reuse_budget; }
+
 // The hit test behind an equal key: the slab's coordinates (staged copies for a host slab)
 // against the fill's snapshot, exactly.  A caller may have rewritten x, y or alt in place
-// behind unchanged pointers.  One synchronisation of S.stream.
-int coords_match(VarCall &v, bool &same) {
-  RecordCache &C = S.cache;
+// behind unchanged pointers.  (The column cache snapshots no alt, nalt = 0: nothing is
+// launched for it.)  One flag read back, one synchronisation of S.stream.
+int cache_coords_match(VarCall &v, Cache &C, bool &same) {
   const auto t0 = std::chrono::steady_clock::now();
   int *flag = C.flag.as<int>();
   HIPCHK(hipMemsetAsync(flag, 0, sizeof(int), S.stream));
@@ -1235,41 +1220,47 @@ int coords_match(VarCall &v, bool &same) {
   HIPCHK(hipMemcpyAsync(C.hflag.p, flag, sizeof(int), hipMemcpyDeviceToHost, S.stream));
   HIPCHK(hipStreamSynchronize(S.stream));
   same = *C.hflag.as<int>() == 0;
-  R.ms_compare = ms_since(t0);
+  (C.per_column ? CR.ms_compare : R.ms_compare) = ms_since(t0);
   return CWBL_OK;
 }
 
-// A call whose key or coordinates differ from the cache's: plans which leading batches'
-// records fit the budget, allocates what they need (kept from an earlier fill when it is
-// large enough) and takes the coordinate snapshot.  The batches then assemble into their own
-// regions instead of S.wsa.  A failed allocation is no error: the call runs without reuse.
-int begin_fill(VarCall &v, const RecordKey &key, CacheForm form) {
-  RecordCache &C = S.cache;
+// A call of the cache v.cache whose key or coordinates differ from the cache's: plans which
+// leading batches' records fit the budget, allocates what they need (kept from an earlier fill
+// when it is large enough) and takes the coordinate snapshot.  The batches then assemble, or
+// fill their factors, into their own regions instead of S.wsa or S.wsf.  A failed allocation is
+// no error: nothing is held and the call runs without reuse.
+int begin_cache_fill(VarCall &v, const CacheKey &key, CacheForm form) {
+  Cache &C = *v.cache;
+  const size_t budget = cache_budget(C);
   C.valid = false;
   C.key = key;
   C.plan = v.plan;
   C.off.clear();
-  C.pts = 0;
+  C.units = 0;
   C.form = form;
   size_t words = 0;
   for (const auto &b : v.plan) {
     // (+1: the spare record; the wave kernels read none, the region's layout is one)
     const size_t need = ((size_t)b.second + 1) * C.words();
-    if ((words + need) * sizeof(double) > S.reuse_budget) break;
+    if ((words + need) * sizeof(double) > budget) break;
     C.off.push_back(words);
     words += need;
-    C.pts += b.second;
+    C.units += b.second;
   }
-  if (C.off.empty()) return CWBL_OK;
+  if (C.off.empty()) {
+    // no batch fits: the record cache keeps an earlier fill's buffers for the next one, the
+    // column cache holds nothing
+    if (C.per_column) C.release();
+    return CWBL_OK;
+  }
   const cwbl_slab *sl = v.sl;
   C.nxy = (size_t)sl->nx * sl->ny;
-  C.nalt = (size_t)sl->alt_nx * sl->alt_ny * sl->nz;
+  C.nalt = C.per_column ? 0 : (size_t)sl->alt_nx * sl->alt_ny * sl->nz;
   // Grow-only, with 1/16 of headroom within the budget: the slabs of one cycle differ by a
   // staggered row, column or level (2 % at 300 x 300 x 50), and replacing the buffer is dear
   // (bench.py's cycle leg once lost 1.6 s to the regrow of 31 GB for a 51-level slab)
   const size_t need = words * sizeof(double);
-  bool ok = need <= C.rec.n ||
-            C.rec.ensure(std::min(S.reuse_budget, need + need / 16)) == hipSuccess;
+  bool ok = need <= C.rec.n || C.rec.ensure(std::min(budget, need + need / 16)) == hipSuccess;
   // The steps' scalars of the factors, an entry per record: beside the budget's cut, like info
   // and the snapshot, with the same headroom; a cache of records holds none
   if (form_has_aux(form)) {
@@ -1279,7 +1270,7 @@ int begin_fill(VarCall &v, const RecordKey &key, CacheForm form) {
   } else {
     C.aux.release();
   }
-  ok = ok && C.info.ensure((size_t)C.pts * sizeof(int2)) == hipSuccess;
+  ok = ok && C.info.ensure((size_t)C.units * sizeof(int2)) == hipSuccess;
   ok = ok && C.sx.ensure(C.nxy * 4) == hipSuccess && C.sy.ensure(C.nxy * 4) == hipSuccess;
   ok = ok && C.salt.ensure(C.nalt * 4) == hipSuccess && C.flag.ensure(sizeof(int)) == hipSuccess;
   ok = ok && C.hflag.ensure(64) == hipSuccess;
@@ -1300,10 +1291,10 @@ int begin_fill(VarCall &v, const RecordKey &key, CacheForm form) {
 // The info window that opens at point g on a hit: the cached points' accepted counts, which
 // solve_tq40_kernel reads where the assembly would have left them.
 int restore_info(VarCall &v, long long g) {
-  const long long pts = v.colcache ? S.ccache.cols : S.cache.pts;
-  const int2 *const kept = (v.colcache ? S.ccache.info : S.cache.info).as<int2>();
-  const long long n = std::min<long long>(v.info_cap, pts - g);
-  if (v.reuse != 2 || n <= 0) return CWBL_OK;
+  if (v.reuse != 2) return CWBL_OK;
+  const int2 *const kept = v.cache->info.as<int2>();
+  const long long n = std::min<long long>(v.info_cap, v.cache->units - g);
+  if (n <= 0) return CWBL_OK;
   HIPCHK(hipMemcpyAsync(S.info.p, kept + g, (size_t)n * sizeof(int2),
                         hipMemcpyDeviceToDevice, S.stream));
   return CWBL_OK;
@@ -1311,10 +1302,10 @@ int restore_info(VarCall &v, long long g) {
 
 // The info window [v.win0, end) as a fill's solves left it (p is what the assembly wrote).
 int keep_info(VarCall &v, long long end) {
-  const long long pts = v.colcache ? S.ccache.cols : S.cache.pts;
-  int2 *const kept = (v.colcache ? S.ccache.info : S.cache.info).as<int2>();
-  const long long n = std::min<long long>(end, pts) - v.win0;
-  if (v.reuse != 1 || n <= 0) return CWBL_OK;
+  if (v.reuse != 1) return CWBL_OK;
+  int2 *const kept = v.cache->info.as<int2>();
+  const long long n = std::min<long long>(end, v.cache->units) - v.win0;
+  if (n <= 0) return CWBL_OK;
   HIPCHK(hipMemcpyAsync(kept + v.win0, S.info.p, (size_t)n * sizeof(int2),
                         hipMemcpyDeviceToDevice, S.stream));
   return CWBL_OK;
@@ -1747,6 +1738,16 @@ long long record_sub_batch(int nb) {
   const long long cap = std::min<long long>(S.tq4_sub > 0 ? S.tq4_sub : nb, 1 << 19);
   return std::min<long long>(sub_batch(nb, cap), 1 << 19);
 }
+// The hand-off path's sub-batch of a call of nv variables: CWBL_OPT_BIG_BATCH, and what the
+// hand-off budget holds of its records (cwbl_init: workspace_bytes when the caller gave one,
+// else 13 GB or 40% of the free device memory).  BigHandoff<128, 64> is 134.7 KB per point:
+// 13 GB at the default 98 304-point sub-batch, outside workspace_bytes.
+long long handoff_sub_batch(int nb, int nv) {
+  const size_t rec_bytes = 8 * big_handoff_words(S.kp, nv);
+  const long long fit = std::max<long long>(
+      kListLanes, (long long)(S.handoff_budget / rec_bytes) / kListLanes * kListLanes);
+  return sub_batch(nb, std::min<long long>(S.big_sub, fit));
+}
 
 // letkf_yoyb + letkf_solve (module_letkf_core.f90:300-700) for batch (g0, nb) on S.stream, one
 // path per ensemble-size class:
@@ -1759,7 +1760,7 @@ long long record_sub_batch(int nb) {
 //                group call; CWBL_OPT_SOLVER = 1: the Jacobi eigensolver kernel (k <= 64)
 // b2 / dn: the events around the batch's solve (the record path times its kernel pair
 // between them).  crec: a cached batch's region of the record cache (every sub-batch's), in
-// the call's form (the table above RecordKey; None with a null crec), which a fill (hit false)
+// the call's form (the table above CacheForm; None with a null crec), which a fill (hit false)
 // writes and a hit (no lists, no trees) solves from.  Record path: a fill assembles into crec
 // in S.wsa's place; caux is the region's FactorAux entries (Tq40Factor; else null and unused).
 // One-wavefront path: a fill runs fill_tq_wave_kernel in solve_tq_kernel's place.  Hand-off
@@ -1826,17 +1827,11 @@ int solve_batch_path(VarCall &v, long long g0, int nb, const int *ncnt, const in
     return CWBL_OK;
   }
   if (handoff) {
-    // BigHandoff<128, 64> is 134.7 KB per point (13 GB at the default 98 304-point
-    // sub-batch, outside workspace_bytes); the sub-batch is also bounded by the hand-off
-    // budget (cwbl_init: workspace_bytes when the caller gave one, else 13 GB or 40% of the
-    // free device memory)
     // (a group's record carries the further variables' Q^T x': BigHandoffMulti)
     const int nv = v.group ? group_var_class(v.nvar) : 1;
     const size_t rec_bytes = 8 * big_handoff_words(S.kp, nv);
     const int ci = nv == 2 ? 0 : nv == 4 ? 1 : 2;  // the group kernels' KernelId offset
-    const long long fit = std::max<long long>(
-        kListLanes, (long long)(S.handoff_budget / rec_bytes) / kListLanes * kListLanes);
-    const long long Bs = sub_batch(nb, std::min<long long>(S.big_sub, fit));
+    const long long Bs = handoff_sub_batch(nb, nv);
     // a cached batch of the factor cache: sub-batch s0 starts s0 factors into its region
     const bool bigf = form == CacheForm::BigFactor;
     const size_t fwords = big_factor_words(S.kp);
@@ -1920,79 +1915,6 @@ CacheForm column_form() {
                        : CacheForm::BigFactor;
 }
 
-void make_column_key(ColumnKey &key, const cwbl_var_params *vp, const cwbl_slab *sl) {
-  std::memset(&key, 0, sizeof key);
-  key.gen = S.gen;
-  key.kp = S.kp;
-  key.multi_infl = vp->multi_infl;
-  const int dims[4] = {sl->nx, sl->ny, sl->ix_lim, sl->iy_lim};
-  std::memcpy(key.dims, dims, sizeof dims);
-  std::memcpy(key.gts, vp->gts, sizeof key.gts);
-  std::memcpy(key.radar, vp->radar, sizeof key.radar);
-}
-
-// The hit test behind an equal key: x and y of the slab (staged copies for a host slab) against
-// the fill's snapshot, exactly.  alt is not compared: a 2-D tree never reads it.  One flag read
-// back, one synchronisation of S.stream.
-int column_coords_match(VarCall &v, bool &same) {
-  ColumnCache &C = S.ccache;
-  const auto t0 = std::chrono::steady_clock::now();
-  int *flag = C.flag.as<int>();
-  HIPCHK(hipMemsetAsync(flag, 0, sizeof(int), S.stream));
-  HIPCHK(launch_coord_snapshot(S.stream, false, v.sd.x, C.sx.as<float>(), (long long)C.nxy, flag));
-  HIPCHK(launch_coord_snapshot(S.stream, false, v.sd.y, C.sy.as<float>(), (long long)C.nxy, flag));
-  HIPCHK(hipMemcpyAsync(C.hflag.p, flag, sizeof(int), hipMemcpyDeviceToHost, S.stream));
-  HIPCHK(hipStreamSynchronize(S.stream));
-  same = *C.hflag.as<int>() == 0;
-  CR.ms_compare = ms_since(t0);
-  return CWBL_OK;
-}
-
-// A shared call that does not hit: plans which leading column batches fit the budget, allocates
-// their regions (kept from an earlier fill when large enough) and takes the snapshot of x and y.
-// The batches then assemble, or fill their factors, into their own regions.  Nothing fits, or an
-// allocation fails: no error, nothing is held and the call runs without the cache.
-int begin_column_fill(VarCall &v, const ColumnKey &key) {
-  ColumnCache &C = S.ccache;
-  C.valid = false;
-  C.key = key;
-  C.plan = v.plan;
-  C.off.clear();
-  C.cols = 0;
-  C.form = column_form();
-  const size_t w = form_words(C.form, S.kp);
-  size_t words = 0;
-  for (const auto &b : v.plan) {
-    const size_t need = ((size_t)b.second + 1) * w;  // (+1: the spare entry)
-    if ((words + need) * sizeof(double) > S.column_reuse) break;
-    C.off.push_back(words);
-    words += need;
-    C.cols += b.second;
-  }
-  if (C.off.empty()) {
-    C.release();
-    return CWBL_OK;
-  }
-  C.nxy = (size_t)v.sl->nx * v.sl->ny;
-  // grow-only, with 1/16 of headroom within the budget (begin_fill)
-  const size_t need = words * sizeof(double);
-  bool ok = need <= C.rec.n ||
-            C.rec.ensure(std::min(S.column_reuse, need + need / 16)) == hipSuccess;
-  ok = ok && C.info.ensure((size_t)C.cols * sizeof(int2)) == hipSuccess;
-  ok = ok && C.sx.ensure(C.nxy * 4) == hipSuccess && C.sy.ensure(C.nxy * 4) == hipSuccess;
-  ok = ok && C.flag.ensure(sizeof(int)) == hipSuccess && C.hflag.ensure(64) == hipSuccess;
-  if (!ok) {
-    (void)hipGetLastError();
-    C.release();
-    return CWBL_OK;
-  }
-  HIPCHK(launch_coord_snapshot(S.stream, true, v.sd.x, C.sx.as<float>(), (long long)C.nxy, nullptr));
-  HIPCHK(launch_coord_snapshot(S.stream, true, v.sd.y, C.sy.as<float>(), (long long)C.nxy, nullptr));
-  v.reuse = 1;
-  v.ncached = (long long)C.off.size();
-  return CWBL_OK;
-}
-
 // ---- CWBL_OPT_COLUMN_SHARE ---------------------------------------------------------------------
 // Why a call of one variable does not run once per column, from what is known before the
 // trees are planned (CWBL_COLUMN_SHARED: it may).  The type rule restates build_family's
@@ -2074,12 +1996,7 @@ int solve_batch_column_factor(VarCall &v, long long g0, int nb, const int *ncnt,
   const bool handoff = handoff_path();
   const size_t fwords = handoff ? big_factor_words(S.kp) : wave_factor_words(S.kp);
   const size_t rec_bytes = handoff ? 8 * big_handoff_words(S.kp, 1) : 0;
-  long long Bs = nb;
-  if (handoff) {  // solve_batch_path's sub-batch of a single call
-    const long long fit = std::max<long long>(
-        kListLanes, (long long)(S.handoff_budget / rec_bytes) / kListLanes * kListLanes);
-    Bs = sub_batch(nb, std::min<long long>(S.big_sub, fit));
-  }
+  const long long Bs = handoff ? handoff_sub_batch(nb, 1) : nb;  // (solve_batch_path's)
   // (+1: the spare entry, as the record cache's regions have one)
   if (!crec &&
       S.wsf.ensure((size_t)(std::min<long long>(Bs, nb) + 1) * fwords * 8) != hipSuccess) {
@@ -2309,10 +2226,8 @@ int finish_call(VarCall &v, cwbl_stats &st) {
   st.solved = (long long)ds.solved * lev;
   st.nobs_sum = (long long)ds.nobs_sum * lev;
   // (a hit ran none, or only the uncached batches', of the searches that count this: the
-  // inputs being equal, the fill's total holds)
-  st.lz_truncated = v.reuse != 2   ? (long long)ds.lz_truncated * lev
-                    : v.colcache ? S.ccache.lz_truncated * lev
-                                 : S.cache.lz_truncated;
+  // inputs being equal, the fill's total per level holds)
+  st.lz_truncated = (v.reuse != 2 ? (long long)ds.lz_truncated : v.cache->lz_truncated) * lev;
   st.nonconverged = (long long)ds.nonconverged * lev;
   st.sweeps_sum = (long long)ds.sweeps_sum * lev;
   st.max_p = (int)ds.max_p;
@@ -2763,7 +2678,7 @@ static int plan_hit_merge(VarCall &v, CacheForm form) {
 // that the call writes once (each launch its own entries), into a table that only grows.
 static int solve_hits_merged(VarCall &v, long long b0, long long b1, hipEvent_t b2,
                              hipEvent_t dn) {
-  RecordCache &C = S.cache;
+  const Cache &C = *v.cache;
   HitSeg *const hseg = S.hitseg_pin.as<HitSeg>() + v.hitseg_used;
   int nseg = 0, maxns = 0;
   long long pts = 0;
@@ -2793,6 +2708,57 @@ static int solve_hits_merged(VarCall &v, long long b0, long long b1, hipEvent_t 
   return CWBL_OK;
 }
 
+// A call of the cache v.cache: an equal key makes it a candidate; the coordinates decide.  A
+// candidate stages its slab first (staged), so its ms_prep holds the staging and the compare.
+// The column cache's equal key means the fill's trees were confirmed 2-D under the same obs set,
+// options and type parameters, so the slab is staged as a shared call's before the trees are
+// planned.  A call that does not hit invalidates the cache: it fills it, if anything does.
+static int cache_candidate(VarCall &v, const CacheKey &key, bool &staged) {
+  Cache &C = *v.cache;
+  if (C.valid && std::memcmp(&key, &C.key, sizeof key) == 0) {
+    if (C.per_column) v.colshare = S.column_share;
+    if (int rc = stage_slab(v)) return rc;
+    staged = true;
+    bool same = false;
+    if (int rc = cache_coords_match(v, C, same)) return rc;
+    if (same) {
+      v.reuse = 2;
+      v.ncached = (long long)C.off.size();
+      v.full_hit = C.off.size() == C.plan.size();
+    }
+  }
+  if (v.reuse != 2) C.valid = false;
+  return CWBL_OK;
+}
+
+// Behind finish_call: a fill is complete, so the next call may solve from it; and what the call
+// reports of its cache (cwbl_reuse_info, cwbl_column_reuse_info; nbat: the call's batches).
+static void complete_cache_call(VarCall &v, const cwbl_stats &st, long long nbat) {
+  if (v.reuse == 1) {
+    Cache &C = *v.cache;
+    C.nt = v.nt;
+    C.list_cap = v.list_cap;
+    // (per level, as finish_call reads it; a shared call is never in the Q1 undefined case: 0)
+    C.lz_truncated = st.lz_truncated / std::max(v.nlev, 1);
+    C.q1_undefined = st.q1_undefined;
+    C.valid = true;
+  }
+  if (v.colcache) {
+    if (v.reuse == 1) CR.columns_filled = v.cache->units;
+    if (v.reuse == 2) CR.columns_reused = v.cache->units;
+    if (v.reuse == 2) CR.batches_reused = v.ncached;
+  }
+  R.batches_reused = v.reuse == 2 && !v.colcache ? v.ncached : 0;  // (the record cache's)
+  R.batches_assembled = nbat - R.batches_reused;
+}
+
+// The list buffers of batch b: the searches alternate between two pairs.
+struct ListBufs { int *cnt, *idx; };
+static ListBufs list_buffers(long long b) {
+  return (b & 1) ? ListBufs{S.nbr_cnt2.as<int>(), S.nbr_idx2.as<int>()}
+                 : ListBufs{S.nbr_cnt.as<int>(), S.nbr_idx.as<int>()};
+}
+
 // The driver of cwbl_analyze_var and of the group calls of cwbl_analyze_vars (v.vp, v.sl, and
 // for a group v.nvar, v.group and the flags of v.tv are the caller's; the arguments are
 // checked).  A group call runs with record reuse off: the cache is not read, filled or
@@ -2806,15 +2772,10 @@ static int analyze_call(VarCall &v, cwbl_stats *stats) {
   std::memset(&st, 0, sizeof st);
   const long long npts = (long long)sl->ix_lim * sl->iy_lim * sl->nz;
   st.points = v.npts = npts;
-  RecordCache &C = S.cache;
-  ColumnCache &CC = S.ccache;
   auto finish = [&]() {
-    R.bytes_held = (long long)C.bytes();
-    CR.bytes_held = (long long)CC.bytes();
-    CR.form = CC.form == CacheForm::Records      ? CWBL_COLUMN_FORM_RECORDS
-              : CC.form == CacheForm::WaveFactor ? CWBL_COLUMN_FORM_WAVE
-              : CC.form == CacheForm::BigFactor  ? CWBL_COLUMN_FORM_BIG
-                                                 : CWBL_COLUMN_FORM_NONE;
+    R.bytes_held = (long long)S.cache.bytes();
+    CR.bytes_held = (long long)S.ccache.bytes();
+    CR.form = form_column_code(S.ccache.form);
     st.ms_total =
         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
     if (stats) *stats = st;
@@ -2836,57 +2797,27 @@ static int analyze_call(VarCall &v, cwbl_stats *stats) {
   hipEvent_t e0, e1, e2, e_ready;
   HIPCHK(event(0, &e0));
   HIPCHK(hipEventRecord(e0, S.stream));
-  // Record reuse: an equal key makes the call a candidate; the coordinates decide.  (A
-  // candidate stages its slab first, so its ms_prep holds the staging and the compare.)
   // Column sharing (CWBL_OPT_COLUMN_SHARE): a candidate runs with record reuse off, as a group
-  // call does; the planned trees confirm it below.
+  // call does; the planned trees confirm it below.  The call's cache: the column cache
+  // (CWBL_OPT_COLUMN_REUSE) for a candidate on a path that option serves, the record cache for a
+  // single-variable call that is none; no other call reads, fills or invalidates either.
   CI.reason = column_reason(v);
   const bool col_candidate = CI.reason == CWBL_COLUMN_SHARED;
-  const CacheForm form = call_form();
-  const bool reuse_on =
-      !v.group && !col_candidate && form != CacheForm::None && S.reuse_budget > 0 && npts > 0;
-  RecordKey key;
+  v.colcache = col_candidate && !v.group && column_reuse_path() && npts > 0;
+  const CacheForm form = v.colcache ? column_form() : call_form();
+  if (v.colcache)
+    v.cache = &S.ccache;
+  else if (!v.group && !col_candidate && form != CacheForm::None && S.reuse_budget > 0 && npts > 0)
+    v.cache = &S.cache;
+  CacheKey key;
   bool staged = false;
-  if (reuse_on) {
-    make_record_key(key, vp, sl);
-    if (C.valid && std::memcmp(&key, &C.key, sizeof key) == 0) {
-      if (int rc = stage_slab(v)) return rc;
-      staged = true;
-      bool same = false;
-      if (int rc = coords_match(v, same)) return rc;
-      if (same) {
-        v.reuse = 2;
-        v.ncached = (long long)C.off.size();
-        v.full_hit = C.off.size() == C.plan.size();
-      }
-    }
-    if (v.reuse != 2) C.valid = false;
-  }
-  // The column cache (CWBL_OPT_COLUMN_REUSE): a candidate for sharing on a path the option serves.
-  // An equal key means the fill's trees were confirmed 2-D under the same obs set, options and
-  // type parameters, so the slab is staged as a shared call's before the trees are planned.
-  const bool creuse_on = col_candidate && !v.group && column_reuse_path() && npts > 0;
-  ColumnKey ckey;
-  if (creuse_on) {
-    make_column_key(ckey, vp, sl);
-    v.colcache = true;
-    if (CC.valid && std::memcmp(&ckey, &CC.key, sizeof ckey) == 0) {
-      v.colshare = S.column_share;
-      if (int rc = stage_slab(v)) return rc;
-      staged = true;
-      bool same = false;
-      if (int rc = column_coords_match(v, same)) return rc;
-      if (same) {
-        v.reuse = 2;
-        v.ncached = (long long)CC.off.size();
-        v.full_hit = CC.off.size() == CC.plan.size();
-      }
-    }
-    if (v.reuse != 2) CC.valid = false;
+  if (v.cache) {
+    make_cache_key(key, vp, sl, v.colcache);
+    if (int rc = cache_candidate(v, key, staged)) return rc;
   }
   if (v.full_hit) {
-    v.nt = v.colcache ? CC.nt : C.nt;
-    v.list_cap = v.colcache ? CC.list_cap : C.list_cap;
+    v.nt = v.cache->nt;
+    v.list_cap = v.cache->list_cap;
   } else if (int rc = plan_trees(v)) {
     return rc;
   }
@@ -2898,7 +2829,7 @@ static int analyze_call(VarCall &v, cwbl_stats *stats) {
     return finish();
   }
   for (const TreeDesc &d : v.descs) st.q1_undefined += d.q1_undef ? npts : 0;
-  if (v.full_hit) st.q1_undefined = v.colcache ? 0 : C.q1_undefined;  // (shared: never Q1)
+  if (v.full_hit) st.q1_undefined = v.cache->q1_undefined;  // (the column cache's: 0)
   // The planned trees decide whether the call is shared per column, and name the Q1 case.  (A
   // candidate with a tree that is not 2-D would mean column_reason and build_family disagree:
   // it runs per point like any other call that is not eligible, with its record reuse off.)
@@ -2911,6 +2842,7 @@ static int analyze_call(VarCall &v, cwbl_stats *stats) {
   v.colshare = CI.reason == CWBL_COLUMN_SHARED ? S.column_share : 0;
   if (!v.colshare && v.colcache) {  // not shared after all: per point, and no column cache
     v.colcache = false;
+    v.cache = nullptr;
     v.reuse = 0;
     v.ncached = 0;
   }
@@ -2930,14 +2862,14 @@ static int analyze_call(VarCall &v, cwbl_stats *stats) {
     CI.levels = v.nlev;
   }
   plan_batches(v);
-  if (v.reuse == 2 && !v.colcache && v.plan != C.plan)
-    return fail(CWBL_ERR_STATE, "record reuse: the batch plan changed under an equal key");
-  if (v.reuse == 2 && v.colcache && v.plan != CC.plan) {
-    // another batch plan under an equal key: a miss.  (A full hit planned no trees yet; the
-    // plan follows their list capacity.)
+  if (v.reuse == 2 && v.plan != v.cache->plan) {
+    // another batch plan under an equal key: the record cache's call fails; the column cache's
+    // is a miss.  (A full hit planned no trees yet; the plan follows their list capacity.)
+    if (!v.colcache)
+      return fail(CWBL_ERR_STATE, "record reuse: the batch plan changed under an equal key");
     v.reuse = 0;
     v.ncached = 0;
-    CC.valid = false;
+    v.cache->valid = false;
     if (v.full_hit) {
       v.full_hit = false;
       if (int rc = plan_trees(v)) return rc;
@@ -2948,10 +2880,8 @@ static int analyze_call(VarCall &v, cwbl_stats *stats) {
   }
   if (int rc = stage_bounce(v)) return rc;
   if (int rc = alloc_call_buffers(v)) return rc;
-  if (reuse_on && v.reuse != 2)
-    if (int rc = begin_fill(v, key, form)) return rc;
-  if (v.colcache && v.reuse != 2)
-    if (int rc = begin_column_fill(v, ckey)) return rc;
+  if (v.cache && v.reuse != 2)
+    if (int rc = begin_cache_fill(v, key, form)) return rc;
   if (int rc = plan_hit_merge(v, form)) return rc;
   if (int rc = restore_info(v, 0)) return rc;
   HIPCHK(event(3, &e_ready));  // inputs staged and the counters cleared
@@ -2978,21 +2908,19 @@ static int analyze_call(VarCall &v, cwbl_stats *stats) {
       if (int rc = restore_info(v, g0)) return rc;
     }
     int2 *const infob = S.info.as<int2>() + (g0 - v.win0);  // this batch's info
-    int *ncnt = (bi & 1) ? S.nbr_cnt2.as<int>() : S.nbr_cnt.as<int>();
-    int *nidx = (bi & 1) ? S.nbr_idx2.as<int>() : S.nbr_idx.as<int>();
+    int *const ncnt = list_buffers(bi).cnt, *const nidx = list_buffers(bi).idx;
     const int ev = v.ev;
     hipEvent_t a, b, b2, dn;
     HIPCHK(event(ev, &a));
     HIPCHK(event(ev + 1, &b));
     HIPCHK(event(ev + 2, &b2));
     HIPCHK(event(ev + 3, &dn));
-    // a cached batch: its region of the record cache; on a hit neither lists nor assembly
-    double *const crec = bi >= v.ncached ? nullptr
-                         : v.colcache    ? CC.rec.as<double>() + CC.off[bi]
-                                         : C.rec.as<double>() + C.off[bi];
-    const bool has_aux = crec && !v.colcache && form_has_aux(form);
-    const size_t aoff = has_aux ? C.off[bi] / C.words() * FactorAux<kTq4KP>::WORDS : 0;
-    double *const caux = has_aux ? C.aux.as<double>() + aoff : nullptr;
+    // a cached batch: its region of the call's cache; on a hit neither lists nor assembly
+    const Cache *const C = bi < v.ncached ? v.cache : nullptr;
+    double *const crec = C ? C->rec.as<double>() + C->off[bi] : nullptr;
+    const bool has_aux = C && form_has_aux(form);
+    const size_t aoff = has_aux ? C->off[bi] / C->words() * FactorAux<kTq4KP>::WORDS : 0;
+    double *const caux = has_aux ? C->aux.as<double>() + aoff : nullptr;
     const bool hit = crec && v.reuse == 2;
     if (hit && v.merge) {
       // the cached batches of this window: [bi, be)
@@ -3000,9 +2928,8 @@ static int analyze_call(VarCall &v, cwbl_stats *stats) {
       while (be < v.ncached && v.plan[be].first + v.plan[be].second - v.win0 <= v.info_cap) ++be;
       // a partial hit: the first batch past the cached ones is searched while they are solved
       if (be == v.ncached && be < nbat) {
-        int *const nc = (be & 1) ? S.nbr_cnt2.as<int>() : S.nbr_cnt.as<int>();
-        int *const ni = (be & 1) ? S.nbr_idx2.as<int>() : S.nbr_idx.as<int>();
-        if (int rc = search_batch(v, be, nc, ni, a, b)) return rc;
+        const ListBufs nl = list_buffers(be);
+        if (int rc = search_batch(v, be, nl.cnt, nl.idx, a, b)) return rc;
         v.search_ev.push_back({ev, ev + 1});
         searched = be;
         searched_ev = b;
@@ -3052,26 +2979,7 @@ static int analyze_call(VarCall &v, cwbl_stats *stats) {
     v.ev += v.tune_batch ? 5 : 4;
   }
   if (int rc = finish_call(v, st)) return rc;
-  if (v.colcache) {  // the column cache's fill is complete, or its hit is reported
-    if (v.reuse == 1) {
-      CC.nt = v.nt;
-      CC.list_cap = v.list_cap;
-      CC.lz_truncated = st.lz_truncated / std::max(v.nlev, 1);
-      CC.valid = true;
-      CR.columns_filled = CC.cols;
-    } else if (v.reuse == 2) {
-      CR.columns_reused = CC.cols;
-      CR.batches_reused = v.ncached;
-    }
-  } else if (v.reuse == 1) {  // the fill is complete: the next call may solve from it
-    C.nt = v.nt;
-    C.list_cap = v.list_cap;
-    C.lz_truncated = st.lz_truncated;
-    C.q1_undefined = st.q1_undefined;
-    C.valid = true;
-  }
-  R.batches_reused = v.reuse == 2 && !v.colcache ? v.ncached : 0;  // (the record cache's)
-  R.batches_assembled = nbat - R.batches_reused;
+  complete_cache_call(v, st, nbat);
   return finish();
 }
 
