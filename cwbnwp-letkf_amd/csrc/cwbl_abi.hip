@@ -264,7 +264,7 @@ struct KTime { long long launches = 0, points = 0; double ms = 0.0; };
 //                                                               the level kernel from level 1;
 //                                                               the all-levels kernel
 //   BigFactor   k = 65..96                 BigFactor<96, 32>    the hand-off kernel,
-//                                                               fill_tqb_tail_kernel and the level
+//               k = 97..128, COLUMN_ROWS   BigFactor<128, 64>   fill_tqb_tail_kernel and the level
 //                                                               kernel from level 1; the
 //                                                               all-levels kernel
 // Its key holds 0 for nz, alt_nx and alt_ny, and its snapshot no alt: a 2-D tree reads neither
@@ -405,6 +405,8 @@ struct State {
   int column_levels = 0;          // CWBL_OPT_COLUMN_LEVELS: levels per wave (0: automatic)
   bool column_factor = false;     // CWBL_OPT_COLUMN_FACTOR: a shared call's levels from one kept
                                   // factor per column (k = 41..96)
+  bool column_rows = false;       // CWBL_OPT_COLUMN_ROWS: k = 97..128 is eligible for
+                                  // CWBL_OPT_COLUMN_FACTOR and CWBL_OPT_COLUMN_REUSE
   int ncu = 0;                    // compute units of the device (automatic level split)
   size_t column_reuse = 0;        // CWBL_OPT_COLUMN_REUSE in bytes (0: off)
   Cache cache{false};   // the record cache (CWBL_OPT_RECORD_REUSE)
@@ -1901,13 +1903,22 @@ int solve_batch_path(VarCall &v, long long g0, int nb, const int *ncnt, const in
   return CWBL_OK;
 }
 
+// The hand-off path's classes whose shared calls solve every level from one kept factor per
+// column: KP = 96, and KP = 128 (k = 97..128) where CWBL_OPT_COLUMN_ROWS admits it.  The option
+// does nothing on its own (CWBL_OPT_COLUMN_FACTOR or CWBL_OPT_COLUMN_REUSE has to be set) and is
+// accepted and ignored at the other KP and on every other path.
+bool handoff_column_path() {
+  return handoff_path() && (S.kp == 96 || (S.kp == kBigSplitKP && S.column_rows));
+}
+
 // ---- CWBL_OPT_COLUMN_REUSE ---------------------------------------------------------------------
 // The classes whose column-shared calls fill and read the column cache: the paths with a
 // per-column form and a kernel that solves every level from it.  Accepted and ignored elsewhere
-// (k <= 16, CWBL_OPT_SPLIT40 = 0, CWBL_OPT_SOLVER = 1, CWBL_OPT_BIG_PATH = 0, k = 97..128).
+// (k <= 16, CWBL_OPT_SPLIT40 = 0, CWBL_OPT_SOLVER = 1, CWBL_OPT_BIG_PATH = 0, k = 97..128; the
+// last is served under CWBL_OPT_COLUMN_ROWS = 1).
 bool column_reuse_path() {
   return S.column_reuse > 0 && S.column_share != 0 &&
-         (record_path() || (wave_path() && S.kp > kTq4KP) || (handoff_path() && S.kp == 96));
+         (record_path() || (wave_path() && S.kp > kTq4KP) || handoff_column_path());
 }
 CacheForm column_form() {
   return record_path() ? CacheForm::Records
@@ -1955,15 +1966,17 @@ int column_levels_per_wave(int ncol, int nz) {
 // CWBL_OPT_COLUMN_FACTOR: a shared call's levels from one kept factor per column, where the
 // path has a factor form with a fill and a hit kernel and the level kernel met its bar
 // (DESIGN.md §3.6): the one-wavefront path at KP = 48, 56, 64 and the hand-off path at KP = 96.
-// Accepted and ignored elsewhere (k <= 40, k = 97..128).
+// Accepted and ignored elsewhere (k <= 40, k = 97..128; the last is served under
+// CWBL_OPT_COLUMN_ROWS = 1).
 bool column_factor_path() {
-  return S.column_factor && ((wave_path() && S.kp > kTq4KP) || (handoff_path() && S.kp == 96));
+  return S.column_factor && ((wave_path() && S.kp > kTq4KP) || handoff_column_path());
 }
 
 // Levels per wavefront of a level kernel's launch over ncol columns and the nl = nz - 1 levels
 // above level 0, one column per wavefront: the option, or all nl unless the columns are fewer
-// than twice the wavefronts the device holds of the kernel (TqOccupancy per SIMD); then the
-// fewest level ranges that reach that many.
+// than twice the wavefronts the device holds of the kernel (TqOccupancy per SIMD: three at
+// KP = 48, two at every other KP, KP = 128 among them); then the fewest level ranges that reach
+// that many.
 int factor_levels_per_wave(int ncol, int nl) {
   int lw = nl;
   if (S.column_levels > 0) {
@@ -2067,7 +2080,8 @@ int solve_batch_column_factor(VarCall &v, long long g0, int nb, const int *ncnt,
 // infob are the columns'.
 //   record path, option 1   assemble_record_kernel over the columns as it is, then
 //                           solve_tq40_column_kernel over the same records with the whole slab
-//   CWBL_OPT_COLUMN_FACTOR  (either option at k = 41..96) solve_batch_column_factor above; the
+//   CWBL_OPT_COLUMN_FACTOR  (either option at k = 41..96, and at k = 97..128 under
+//                           CWBL_OPT_COLUMN_ROWS) solve_batch_column_factor above; the
 //                           chunks below only if its workspace cannot be allocated
 //   chunked paths           (option 1 elsewhere, option 2 everywhere) the levels in chunks of up
 //                           to kMaxGroupVars: each chunk is the path's group launch on the column
@@ -2326,6 +2340,7 @@ int cwbl_init(const cwbl_init_params *p) {
   S.column_share = 0;
   S.column_levels = 0;
   S.column_factor = false;
+  S.column_rows = false;
   S.column_reuse = 0;
   S.factor_reuse = true;
   S.hit_merge = true;
@@ -2470,6 +2485,17 @@ int cwbl_set_option(int option, long long value) {
       S.column_reuse = (size_t)value << 20;
       (void)hipStreamSynchronize(S.stream);
       S.ccache.release();  // 0 holds no memory; the next fill allocates within the new budget
+      return CWBL_OK;
+    case CWBL_OPT_COLUMN_ROWS:
+      // (which classes fill and read the column cache: a new generation, like every option that
+      // decides what is cached)
+      if (!range(0, 1)) break;
+      (void)hipStreamSynchronize(S.stream);
+      S.column_rows = value == 1;
+      if (!S.column_rows && S.kp == kBigSplitKP) {  // off holds no memory
+        S.wsf.release();
+        S.ccache.release();
+      }
       return CWBL_OK;
     default:
       return fail(CWBL_ERR_ARG, "cwbl_set_option: unknown option %d", option);

@@ -511,26 +511,33 @@ hipError_t launch_solve_tqb_factor_rows(hipStream_t s, SolveConsts c, SlabDev sl
 // from its factor, one column per wavefront and lw levels per wavefront (grid (ncol,
 // ceil((nz - 1) / lw)); the bits do not depend on lw).  slab is the whole slab (nz levels);
 // info is read only.  cwbl_tq_wave_column.hip (KP = 48, 56, 64: solve_tq_wave_factor_kernel's
-// replay and tq_wave_finish per level) and cwbl_tq_big_column.hip (KP = 96: tqb_factor_hit per
-// level).
+// replay and tq_wave_finish per level), cwbl_tq_big_column.hip (KP = 96: tqb_factor_hit per
+// level) and cwbl_tq_rows_column.hip (KP = 128, CWBL_OPT_COLUMN_ROWS: tqb_rows_hit per level;
+// launch_*_rows, which the KP launcher passes on to).
 hipError_t launch_solve_tq_wave_factor_column(hipStream_t s, int kp, SolveConsts c, SlabDev slab,
                                               long long g0, int ncol, int nz, int lw,
                                               const double *fac, const int2 *info);
 hipError_t launch_solve_tqb_factor_column(hipStream_t s, int kp, SolveConsts c, SlabDev slab,
                                           long long g0, int ncol, int nz, int lw,
                                           const double *fac, const int2 *info);
+hipError_t launch_solve_tqb_factor_column_rows(hipStream_t s, SolveConsts c, SlabDev slab,
+                                               long long g0, int ncol, int nz, int lw,
+                                               const double *fac, const int2 *info);
 
 // A column-shared call that hits the column cache (CWBL_OPT_COLUMN_REUSE): the two kernels above
 // started at level 0, since no fill of this call analysed it.  `fac` and info[i].x are what an
 // earlier call's fill left for the ncol columns from g0; these solve the levels 0 .. nz-1 of
-// every column (grid (ncol, ceil(nz / lw))).  cwbl_tq_wave_column_all.hip (KP = 48, 56, 64) and
-// cwbl_tq_big_column_all.hip (KP = 96).
+// every column (grid (ncol, ceil(nz / lw))).  cwbl_tq_wave_column_all.hip (KP = 48, 56, 64),
+// cwbl_tq_big_column_all.hip (KP = 96) and cwbl_tq_rows_column.hip (KP = 128).
 hipError_t launch_solve_tq_wave_factor_column_all(hipStream_t s, int kp, SolveConsts c,
                                                   SlabDev slab, long long g0, int ncol, int nz,
                                                   int lw, const double *fac, const int2 *info);
 hipError_t launch_solve_tqb_factor_column_all(hipStream_t s, int kp, SolveConsts c, SlabDev slab,
                                               long long g0, int ncol, int nz, int lw,
                                               const double *fac, const int2 *info);
+hipError_t launch_solve_tqb_factor_column_all_rows(hipStream_t s, SolveConsts c, SlabDev slab,
+                                                   long long g0, int ncol, int nz, int lw,
+                                                   const double *fac, const int2 *info);
 
 // KP = 96, 128: one 256-thread workgroup per point (cwbl_tq_big.hip)
 hipError_t launch_solve_tq_big(hipStream_t s, int kp, bool assembled, const TreeDesc *trees,

@@ -54,6 +54,9 @@ solve_tqb_factor_column_kernel(SolveConsts c, SlabDev slab, long long g0, int nc
 hipError_t launch_solve_tqb_factor_column(hipStream_t s, int kp, SolveConsts c, SlabDev slab,
                                           long long g0, int ncol, int nz, int lw,
                                           const double *fac, const int2 *info) {
+  // KP = 128 (CWBL_OPT_COLUMN_ROWS): cwbl_tq_rows_column.hip
+  if (kp == 128)
+    return launch_solve_tqb_factor_column_rows(s, c, slab, g0, ncol, nz, lw, fac, info);
   if (ncol <= 0 || nz < 2) return hipSuccess;
   if (c.quad == nullptr || kp != 96 || c.k <= kp - 62 || !fac || !info || lw < 1 ||
       slab.nz != nz || g0 + ncol > (long long)slab.ix_lim * slab.iy_lim)

@@ -31,7 +31,7 @@ OPT_BIG_PATH, OPT_BIG_BATCH, OPT_PAGEABLE, OPT_BIN_DIV, OPT_LEAD_DIV, OPT_MAX_BA
 OPT_INFO_WINDOW, OPT_INDEX, OPT_RECORD_REUSE = 12, 13, 14
 OPT_COLUMN_SHARE, OPT_COLUMN_LEVELS, OPT_FACTOR_REUSE, OPT_HIT_MERGE = 15, 16, 17, 18
 OPT_WAVE_REUSE, OPT_HOST_PIPE, OPT_BIG_REUSE, OPT_ROWS_REUSE = 19, 20, 21, 22
-OPT_COLUMN_FACTOR, OPT_COLUMN_REUSE = 23, 24
+OPT_COLUMN_FACTOR, OPT_COLUMN_REUSE, OPT_COLUMN_ROWS = 23, 24, 25
 OPTIONS = {"solver": OPT_SOLVER, "split40": OPT_SPLIT40, "split40_batch": OPT_SPLIT40_BATCH,
            "search": OPT_SEARCH,
            "big_path": OPT_BIG_PATH, "big_batch": OPT_BIG_BATCH, "pageable": OPT_PAGEABLE,
@@ -42,7 +42,7 @@ OPTIONS = {"solver": OPT_SOLVER, "split40": OPT_SPLIT40, "split40_batch": OPT_SP
            "hit_merge": OPT_HIT_MERGE, "wave_reuse": OPT_WAVE_REUSE,
            "host_pipe": OPT_HOST_PIPE, "big_reuse": OPT_BIG_REUSE,
            "rows_reuse": OPT_ROWS_REUSE, "column_factor": OPT_COLUMN_FACTOR,
-           "column_reuse": OPT_COLUMN_REUSE}
+           "column_reuse": OPT_COLUMN_REUSE, "column_rows": OPT_COLUMN_ROWS}
 
 #: cwbl_column_info_t.reason
 (COLUMN_SHARED, COLUMN_REASON_OFF, COLUMN_REASON_3D, COLUMN_REASON_Q1, COLUMN_REASON_NZ,

@@ -99,6 +99,10 @@ module letkf_core_gpu
     ! record (k = 17..40) or factor (k = 41..96) for the next call with the same localisation, x
     ! and y, whatever its nz (0, default: off; MU, P and PH then pay one search and reduction)
     integer(c_int), parameter, public :: CWBL_OPT_COLUMN_REUSE = 24
+    ! cwbl_set_option: 1 makes the hand-off path at KP = 128 (ensemble sizes above 96) eligible for
+    ! CWBL_OPT_COLUMN_FACTOR and CWBL_OPT_COLUMN_REUSE, as KP = 96 is (0, default: they are
+    ! ignored there and a shared call runs the level chunks)
+    integer(c_int), parameter, public :: CWBL_OPT_COLUMN_ROWS = 25
     ! cwbl_column_reuse_info_t%form
     integer(c_int), parameter, public :: CWBL_COLUMN_FORM_NONE = 0
     integer(c_int), parameter, public :: CWBL_COLUMN_FORM_RECORDS = 1

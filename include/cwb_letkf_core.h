@@ -489,8 +489,11 @@ enum {
                                 * taken.  Accepted and ignored everywhere else: k <= 40,
                                 * k = 97..128, CWBL_OPT_SOLVER = 1, CWBL_OPT_BIG_PATH = 0, group
                                 * calls and calls that are not shared.  Nothing that is cached
-                                * depends on it: setting it leaves a filled cache valid */
-  CWBL_OPT_COLUMN_REUSE = 24   /* device-memory budget in MiB of the column cache: what a call
+                                * depends on it: setting it leaves a filled cache valid.  With
+                                * CWBL_OPT_COLUMN_ROWS = 1 the hand-off path at KP = 128 is served
+                                * as well, as at KP = 96: fill_tqb_tail_kernel<128, 64> and
+                                * solve_tqb_factor_column_kernel<128, 64> */
+  CWBL_OPT_COLUMN_REUSE = 24,  /* device-memory budget in MiB of the column cache: what a call
                                 * that is shared per column keeps for the next one (0 = off, the
                                 * default; 0 releases what is held; cwbl_init resets it).  The
                                 * weights of such a call depend on the column (i, j) alone, not
@@ -527,7 +530,32 @@ enum {
                                 * invalidated by a column call, and a per-point call never touches
                                 * the column cache.  Accepted and ignored at k <= 16, k = 97..128,
                                 * CWBL_OPT_SPLIT40 = 0, CWBL_OPT_SOLVER = 1, CWBL_OPT_BIG_PATH = 0
-                                * and for group calls */
+                                * and for group calls.  With CWBL_OPT_COLUMN_ROWS = 1 the hand-off
+                                * path at KP = 128 is served as well, as at KP = 96: the kept
+                                * factor is the BigFactor<128, 64> (8705 words, 69.6 KB per column)
+                                * and a hit runs solve_tqb_factor_column_all_kernel<128, 64> */
+  CWBL_OPT_COLUMN_ROWS = 25    /* 1: the hand-off path at KP = 128 (the ensemble sizes above 96
+                                * up to 128, default solver, CWBL_OPT_BIG_PATH = 1) becomes
+                                * eligible for CWBL_OPT_COLUMN_FACTOR and CWBL_OPT_COLUMN_REUSE,
+                                * which then hold there as they hold at KP = 96: the fill of
+                                * CWBL_OPT_ROWS_REUSE (fill_tqb_tail_kernel<128, 64> behind the
+                                * half-row hand-off kernel) analyses level 0 and leaves one
+                                * factor per column, and solve_tqb_factor_column_kernel<128, 64>
+                                * (a column-cache hit: solve_tqb_factor_column_all_kernel
+                                * <128, 64>) solves the levels from it instead of the level
+                                * chunks, which repeat the assembly and the reduction every eight
+                                * levels.  Bit-identical results and equal counters.  It does
+                                * nothing on its own: the two options still have to be set.  The
+                                * workspace of CWBL_OPT_COLUMN_FACTOR is 69.6 KB per column of a
+                                * sub-batch (CWBL_OPT_BIG_BATCH; 6.8 GB at its default); a failed
+                                * allocation still means the level chunks and no error.  The
+                                * per-point cache of CWBL_OPT_ROWS_REUSE is neither read, filled
+                                * nor invalidated by a column call.  0 (default; cwbl_init resets
+                                * it): every call launches what it launches without the option;
+                                * setting 0 releases what the two options hold at KP = 128.
+                                * Accepted and ignored at the ensemble sizes up to 96, under
+                                * CWBL_OPT_BIG_PATH = 0, under CWBL_OPT_SOLVER = 1 and for group
+                                * calls.  Setting it starts a new generation of both caches */
 };
 int         cwbl_set_option(int option, long long value);
 

@@ -12,6 +12,11 @@ above k = 40, and record_reuse = 0 in every mode.  Per k, one process, the modes
   0   this tree's library, column_reuse = 0
   R   column_reuse = --budget MiB: MU fills the column cache, P and PH hit it
 
+At k = 97, 112, 128 (any k > 96) modes 0 and R set column_rows = 1 as well, which makes that
+class eligible for both options: mode 0 is then the shared call from the workspace of
+column_factor, mode P (the parent's library, which has no such option) the level chunks, and the
+output is appended to profiles/column_rows.txt behind scripts/column_share_ab.py --factor's.
+
 Per mode and round: one Core for the whole sequence, one untimed repetition (it sizes every
 buffer), then --reps timed ones.  A repetition restores the three variables (untimed) and starts
 with a fresh cwbl_set_obs, which clears the index cache and voids the column cache, so that the
@@ -80,6 +85,8 @@ class Bench:
             opts["column_factor"] = 1
         if budget is not None:
             opts["column_reuse"] = budget
+            if w.k > 96:  # (this tree's library only: the parent has no such option)
+                opts["column_rows"] = 1
         core = abi.Core(w.k, device=0, lib=lib, options=opts)
         has_info = hasattr(lib, "cwbl_column_reuse_info")
 
@@ -134,8 +141,16 @@ def main():
     ap.add_argument("--budget", type=int, default=16384, help="column_reuse of mode R, MiB")
     ap.add_argument("--parent", default=None, help="the parent commit's libcwbl.so (mode P)")
     ap.add_argument("--scale", type=float, default=None, help="shrink the grid (a quick look)")
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "column_reuse.txt"))
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    ks = [int(s) for s in args.ks.split(",")]
+    rows = max(ks) > 96
+    if args.out is None:
+        args.out = os.path.join(REPO, "profiles", "column_rows.txt" if rows else "column_reuse.txt")
+    before = ""
+    if rows and os.path.exists(args.out):
+        with open(args.out) as f:
+            before = f.read()
     here = abi.load_library()
     modes = [("0", here, 0), ("R", here, args.budget)]
     if args.parent:
@@ -150,12 +165,14 @@ def main():
     what = {"P": "parent commit's library", "0": "column_reuse = 0",
             "R": f"column_reuse = {args.budget} MiB"}
     failed = []
-    for k in (int(s) for s in args.ks.split(",")):
+    for k in ks:
         w = synth.make("c2", k=k, nz=args.nz + 1, vclr=-1.0, scale=args.scale)
         say(f"== c2, vclr = -1: {w.nx}x{w.ny} columns = {w.nx * w.ny}, nz = 1, {args.nz}, "
             f"{args.nz + 1}, k={k}, {w.obs.shape[0]} obs"
             f"{' (scale %g)' % args.scale if args.scale else ''}; column_share = 1"
-            f"{', column_factor = 1' if k > 40 else ''}, record_reuse = 0; reps={args.reps} x "
+            f"{', column_factor = 1' if k > 40 else ''}"
+            f"{', column_rows = 1 (modes 0 and R)' if k > 96 else ''}, record_reuse = 0; "
+            f"reps={args.reps} x "
             f"rounds={args.rounds}; ms per call, median [min .. max]")
         b = Bench(w, args.nz)
         b.run(here, 0, 0, False, False)  # untimed: kernels loaded
@@ -196,7 +213,11 @@ def main():
             else:
                 say(f"   fill / miss = {np.median(hit) / np.median(zero):.3f} (the fill is a "
                     f"shared call of one level; the miss is the per-point call)")
-            if "P" in res:
+            if "P" in res and k > 96:
+                p = res["P"]["ms"][i]
+                say(f"   mode 0 / mode P = {np.median(zero) / np.median(p):.3f} (P: the level "
+                    f"chunks, or for MU the per-point call)")
+            elif "P" in res:
                 p = res["P"]["ms"][i]
                 gap = abs(float(np.median(p) - np.median(zero)))
                 say(f"   |median P - median 0| = {gap:.3f} ms, the parent's run-to-run range "
@@ -205,7 +226,7 @@ def main():
         del b
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:  # (after every k: a later failure keeps what ran)
-            f.write("\n".join(OUT) + "\n")
+            f.write(before + "\n".join(OUT) + "\n")
     assert not failed, failed
 
 

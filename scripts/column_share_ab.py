@@ -10,7 +10,11 @@ modes alternated --rounds times:
   1   column_share = 1: the column kernel (k = 17..40) or the level-chunked group kernels
   2   column_share = 2: the level-chunked group kernels on the record path too
   F   (--factor, in mode 2's place) column_share = 1 with column_factor = 1: every level from
-      one kept factor per column (k = 41..96); the output goes to profiles/column_factor.txt
+      one kept factor per column (k = 41..96); the output goes to profiles/column_factor.txt.
+      At k = 97, 112, 128 (any k > 96) mode F sets column_rows = 1 as well, which makes that
+      class eligible; mode 1 is then the same call without column_rows (the level chunks), mode
+      P1 the parent's library with column_share = 1 (column_rows = 0 costs nothing), and the
+      output goes to profiles/column_rows.txt
 
 Every mode runs with record_reuse = 0 (a shared call runs without the cache; the per-point
 call then pays no cache fill either).  Per mode and round: one library state, one untimed
@@ -72,6 +76,10 @@ class Bench:
         opts = {"record_reuse": 0}
         if share == "F":
             opts.update(column_share=1, column_factor=1)
+            if w.k > 96:
+                opts["column_rows"] = 1
+        elif share == "P1":
+            opts["column_share"] = 1
         elif share is not None:
             opts["column_share"] = share
         core = abi.Core(w.k, device=0, lib=lib, options=opts)
@@ -113,8 +121,11 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--factor", action="store_true", help="mode F in mode 2's place")
     args = ap.parse_args()
+    ks = [int(s) for s in args.ks.split(",")]
+    rows = args.factor and max(ks) > 96
     if args.out is None:
         args.out = os.path.join(REPO, "profiles",
+                                "column_rows.txt" if rows else
                                 "column_factor.txt" if args.factor else "column_share.txt")
     here = abi.load_library()
     modes = [("0", here, 0), ("1", here, 1),
@@ -128,10 +139,15 @@ def main():
                 fn, ours = getattr(parent, name), getattr(here, name)
                 fn.argtypes, fn.restype = ours.argtypes, ours.restype
         modes.insert(0, ("P", parent, None))
+        if rows:
+            modes.insert(1, ("P1", parent, "P1"))
     what = {"P": "parent commit's library", "0": "column_share = 0 (per point)",
             "1": "column_share = 1", "2": "column_share = 2 (level chunks)",
-            "F": "column_share = 1, column_factor = 1"}
-    for k in (int(s) for s in args.ks.split(",")):
+            "F": "column_share = 1, column_factor = 1",
+            "P1": "parent commit's library, column_share = 1"}
+    if rows:
+        what["F"] += ", column_rows = 1 above k = 96"
+    for k in ks:
         w = synth.make("c2", k=k, nz=args.nz, vclr=-1.0, scale=args.scale)
         say(f"== c2, vclr = -1: {w.nx}x{w.ny}x{w.nz} grid = {w.points} points, k={k}, "
             f"{w.obs.shape[0]} obs{' (scale %g)' % args.scale if args.scale else ''}; "
@@ -179,6 +195,11 @@ def main():
             rng = max(max(p) - min(p), max(z) - min(z))
             say(f"   |median P - median 0| = {gap:.3f} ms, run-to-run range {rng:.3f} ms: "
                 f"{'within' if gap <= rng else 'NOT within'}")
+        if "P1" in res:
+            p, z = res["P1"]["ms"], res["1"]["ms"]
+            gap = abs(float(np.median(p) - np.median(z)))
+            say(f"   |median P1 - median 1| = {gap:.3f} ms, the parent's own range "
+                f"{max(p) - min(p):.3f} ms: {'within' if gap <= max(p) - min(p) else 'NOT within'}")
         say()
         del b
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
