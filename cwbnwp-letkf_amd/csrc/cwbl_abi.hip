@@ -23,6 +23,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <memory>
 #include <string>
 #include <vector>
@@ -1153,9 +1154,11 @@ struct VarCall {
   Cache *cache = nullptr;
   bool colcache = false;
   // CWBL_OPT_HIT_MERGE: the call's cached batches go out in one launch per info window;
-  // hitseg_used: entries of S.hitseg_pin taken by the launches so far
+  // hitseg_used: entries of S.hitseg_pin taken by the launches so far; cuts: the traces at which
+  // the call's inflat and k raise a wave's rounds (hit_level_cuts)
   bool merge = false;
   size_t hitseg_used = 0;
+  HitLevelCuts cuts = {};
   // CWBL_OPT_COLUMN_SHARE (1 or 2 when the call is shared, else 0): sd is the column view of
   // the slab (nz = 1; L stays the member stride nx ny nz) and npts its ncol = ix_lim iy_lim
   // points, so the plan, the searches, the lists, the assembly and the info windows are per
@@ -2681,11 +2684,57 @@ static long long hit_segments(int nb, long long *Bs_out = nullptr) {
   return Bs >= nb ? 1 : (nb + Bs - 1) / Bs;
 }
 
+// HitLevelCuts for a call's inflat and k: cuts.t[i] is the smallest trace for which
+// solve_tq40_kernel's level loop (dec = 10, 100, ... while dec < trace / m - (k - 1)) ends above
+// level n = kRoundCuts[i], i.e. for which 10^n < trace / m - (k - 1) in the kernel's two rounded
+// operations.  For m >= 0 neither the quotient nor the difference decreases with the trace (at
+// m = 0 the quotient of a zero trace is NaN, which fails the test between the traces that give
+// -inf and +inf), so the traces that pass are those from the smallest one on: bisection over
+// the doubles in their order.  NaN where not even +inf passes.  False for another m.
+static bool hit_level_cuts(float inflat, int k, HitLevelCuts &cuts) {
+  const double m = (double)inflat, km1 = (double)(k - 1);
+  if (!(m >= 0.0)) return false;
+  // the doubles -inf .. +inf as unsigned integers in the same order, and back
+  auto key = [](double d) {
+    uint64_t b;
+    std::memcpy(&b, &d, sizeof b);
+    return (b >> 63) ? ~b : b | (1ull << 63);
+  };
+  auto val = [](uint64_t u) {
+    const uint64_t b = (u >> 63) ? u & ~(1ull << 63) : ~u;
+    double d;
+    std::memcpy(&d, &b, sizeof d);
+    return d;
+  };
+  for (int i = 0; i < 3; ++i) {
+    double dec = 10.0;  // (the kernel's products: exact)
+    for (int n = 1; n < kRoundCuts[i]; ++n) dec *= 10.0;
+    auto above = [&](double t) {
+      volatile double q = t / m;  // (two rounded operations, as on the device)
+      const double ratio = q - km1;
+      return dec < ratio;
+    };
+    uint64_t lo = key(-HUGE_VAL), hi = key(HUGE_VAL);
+    if (!above(val(hi))) {
+      cuts.t[i] = std::numeric_limits<double>::quiet_NaN();
+      continue;
+    }
+    while (lo < hi) {  // above(val(hi)) holds
+      const uint64_t mid = lo + (hi - lo) / 2;
+      if (above(val(mid))) hi = mid;
+      else lo = mid + 1;
+    }
+    cuts.t[i] = val(hi);
+  }
+  return true;
+}
+
 // Whether the call's cached batches go out merged, and room for their segment tables.
 static int plan_hit_merge(VarCall &v, CacheForm form) {
   // (the other factor forms' hits are one launch per batch or sub-batch)
   v.merge = S.hit_merge && form == CacheForm::Tq40Factor && v.reuse == 2 && !v.group &&
-            !v.colshare && !v.piped && !v.piped_back && !v.bounce && v.ncached > 0;
+            !v.colshare && !v.piped && !v.piped_back && !v.bounce && v.ncached > 0 &&
+            hit_level_cuts(v.c.inflat, v.c.k, v.cuts);
   if (!v.merge) return CWBL_OK;
   long long nseg = 0;
   for (long long bi = 0; bi < v.ncached; ++bi) nseg += hit_segments(v.plan[bi].second);
@@ -2729,7 +2778,7 @@ static int solve_hits_merged(VarCall &v, long long b0, long long b1, hipEvent_t 
   if (S.ktiming) S.kpend.push_back({KT_SOLVE_TQ40_FACTOR, b2, dn, pts});
   HIPCHK(launch_solve_tq40_factor_merged(S.stream, S.kp, v.c, v.sd, dseg, nseg, maxns,
                                          C.rec.as<double>(), C.aux.as<double>(),
-                                         S.info.as<int2>()));
+                                         S.info.as<int2>(), v.cuts));
   HIPCHK(hipEventRecord(dn, S.stream));
   return CWBL_OK;
 }

@@ -319,10 +319,25 @@ struct HitSeg {
   int ns;         // points (<= 2^19)
   int info;       // its info from info[info]
 };
-// seg: the nseg <= 65535 segments, on the device; maxns: the largest one's points.
+// The merged hit takes a solved point's level from the info the fill kept, and needs the trace
+// only for the lanes that have none (p = 0, past the segment), whose level reaches nothing but
+// the wave's rounds: t[i] is the smallest trace(T) from which solve_tq40_kernel's level loop
+// ends above kRoundCuts[i], the levels after which quad_rounds steps (NaN: no trace does).
+constexpr int kRoundCuts[3] = {3, 5, kQuadLevels31};
+static_assert(quad_rounds(1) == quad_rounds(kRoundCuts[0]) &&
+              quad_rounds(kRoundCuts[0] + 1) == quad_rounds(kRoundCuts[1]) &&
+              quad_rounds(kRoundCuts[1] + 1) == quad_rounds(kRoundCuts[2]) &&
+              quad_rounds(kRoundCuts[2] + 1) == quad_rounds(kQuadLevels),
+              "quad_rounds steps after kRoundCuts only");
+struct HitLevelCuts {
+  double t[3];
+};
+// seg: the nseg <= 65535 segments, on the device; maxns: the largest one's points; info: as
+// restore_info left it (p, and the fill's +-level where p > 0).
 hipError_t launch_solve_tq40_factor_merged(hipStream_t s, int kp, SolveConsts c, SlabDev slab,
                                            const HitSeg *seg, int nseg, int maxns,
-                                           const double *ws, const double *aux, int2 *info);
+                                           const double *ws, const double *aux, int2 *info,
+                                           HitLevelCuts cuts);
 
 // cwbl_analyze_vars: the variables of a group share the record (A, b1) and so the factor
 // A = Q T Q^T; solve_tq40_multi_kernel (cwbl_tq40_multi.hip) tridiagonalises once per point

@@ -86,12 +86,15 @@ __device__ __forceinline__ void tq40_load_xb(const SlabDev &slab, const long lon
 // x scal below) where it found x (phase 1: sm.pv's column, phase 2: the column's registers),
 // and the back-transform takes it from there instead of forming the same product again; phase
 // 2's columns may hold any words on the rows above j + 1 (tq40_factor_hit's plain loads).
+// It also takes a solved point's level from ly, the info.y its fill stored, instead of
+// working it out again from the trace (cuts: HitLevelCuts of the call's inflat and k, for the
+// lanes that have no kept level; see there; profiles/hit_masks.txt).
 template <int KP, bool AHEAD, bool LEAN = false>
 __device__ __forceinline__ void tq40_factor_solve(
     const SolveConsts &c, const SlabDev &slab, Tq40Smem<KP> &sm,
     double (&A)[Tq40Layout<KP>::NS][KP], const float (&xbv)[Tq40Layout<KP>::NV], const long long g0,
     const bool valid, const int ptot, const int gi, const int q, const int l,
-    int2 *__restrict__ info) {
+    int2 *__restrict__ info, const int ly = 0, const HitLevelCuts &cuts = HitLevelCuts{}) {
   using LY = Tq40Layout<KP>;
   constexpr int J0 = LY::J0, KT = LY::KT, NS = LY::NS, NV = LY::NV, H = LY::H;
   using SM = Tq40Smem<KP>;
@@ -111,29 +114,54 @@ __device__ __forceinline__ void tq40_factor_solve(
   // unused; every lane of the row holds the same count): one register less across the solve
   int *const pkeep = reinterpret_cast<int *>(&sm.tq[q][KP][3]);
   *pkeep = ptot;
-  double trace;
-  if constexpr (LEAN) {  // tq40_trace through the slots
-    double tp = 0.0;
-    sfor<(KP + 15) / 16>([&](auto rr) {
-      constexpr int r = decltype(rr)::value;
-      const int i = l + 16 * r;
-      if (16 * r + 15 < KP || i < KP)
-        tp += i < k ? sm.tq[q][i < KP ? tq40_slot16<KP, true, 16 * r>(i) : 0][0] : 0.0;
-    });
-    trace = rsum16(tp);
-  } else {
-    trace = tq40_trace(sm, q, l, k);
-  }
+  if constexpr (LEAN) pkeep[1] = ly;  // (and the kept info.y beside it)
 
   // ---- the quadrature rule of the point: T only ---------------------------------------------
   // (twin: this level loop and the walk's LDS offsets below are solve_tq40_kernel's)
   const double m = (double)c.inflat;
-  const double ratio = trace / m - (double)(k - 1);
   int level = 1;
-  double dec = 10.0;
-  while (level < kQuadLevels && dec < ratio) {
-    dec *= 10.0;
-    ++level;
+  double ratio = 0.0, dec = 10.0;
+  if constexpr (LEAN) {
+    // The level is a function of the factor and of inflat, which the cache's key holds, and the
+    // fill's solve has stored it: ly = info.y is +-level on a point with p > 0, as this text
+    // left it there on the fill (negative: M/m beyond the last table), and what is stored at
+    // the end is ly again.  ly = 0 marks the lanes no solve has written for: a point with
+    // p = 0, whose info the assembly left as (0, 0), and a lane past the segment.  Their
+    // records are whatever the cache's memory held (the assembly skips a point with p = 0, the
+    // spare record is never written), so no constant stands for their level; but it reaches
+    // nothing of a stored result except the wave's rounds R, through quad_rounds, which steps
+    // after the levels kRoundCuts alone.  The loop below ends above level n < kQuadLevels
+    // exactly when 10^n < trace / m - (k - 1) (the decades are exact, and each test implies
+    // the one before it).  For m >= 0 the rounded quotient and the rounded difference do not
+    // decrease with the trace, so that holds from a smallest trace on, cuts.t, which the host
+    // finds by bisection with the same two operations; a NaN trace fails the test and the
+    // compare alike.  Such a lane takes the first level of its class of rounds, and its own
+    // rule, sums and analysis, which are never stored, may differ from the loop's.  Only a
+    // wave that has such a lane sums its traces (wave-uniform: no lane is masked off).
+    const bool known = ly != 0;
+    level = min(max(abs(ly), 1), kQuadLevels);
+    if (__ballot(!known)) {
+      double tp = 0.0;  // tq40_trace through the slots
+      sfor<(KP + 15) / 16>([&](auto rr) {
+        constexpr int r = decltype(rr)::value;
+        const int i = l + 16 * r;
+        if (16 * r + 15 < KP || i < KP)
+          tp += i < k ? sm.tq[q][i < KP ? tq40_slot16<KP, true, 16 * r>(i) : 0][0] : 0.0;
+      });
+      const double trace = rsum16(tp);
+      const int lt = trace >= cuts.t[2]   ? kRoundCuts[2] + 1
+                     : trace >= cuts.t[1] ? kRoundCuts[1] + 1
+                     : trace >= cuts.t[0] ? kRoundCuts[0] + 1
+                                          : 1;
+      level = known ? level : lt;
+    }
+  } else {
+    const double trace = tq40_trace(sm, q, l, k);
+    ratio = trace / m - (double)(k - 1);
+    while (level < kQuadLevels && dec < ratio) {
+      dec *= 10.0;
+      ++level;
+    }
   }
   const int R = tq40_wave_rounds(level);
   const int NQ = 8 * R - 1;  // (R is wave-uniform)
@@ -510,7 +538,12 @@ __device__ __forceinline__ void tq40_factor_solve(
       if (i < k) var[P + slab.L * i] = xa[vs];
     });
     // info.y: decade of the quadrature rule (negative when M/m exceeds the last table)
-    if (l == 0) info[gi] = make_int2(pt, ratio > dec ? -level : level);
+    // (LEAN: the kept word, which is that)
+    if constexpr (LEAN) {
+      if (l == 0) info[gi] = make_int2(pt, pkeep[1]);
+    } else {
+      if (l == 0) info[gi] = make_int2(pt, ratio > dec ? -level : level);
+    }
   }
 }
 
@@ -527,7 +560,8 @@ __device__ __forceinline__ void tq40_factor_hit(const SolveConsts &c, const Slab
                                                 const int npts, const double *__restrict__ ws,
                                                 const double *__restrict__ aux,
                                                 int2 *__restrict__ info, const int b,
-                                                const int nblk) {
+                                                const int nblk,
+                                                const HitLevelCuts &cuts = HitLevelCuts{}) {
   using LY = Tq40Layout<KP>;
   using FR = FactorRecord<KP>;
   using FA = FactorAux<KP>;
@@ -540,7 +574,14 @@ __device__ __forceinline__ void tq40_factor_hit(const SolveConsts &c, const Slab
   const int g4 = xcd_remap_rev(b, nblk);
   const int gi = 4 * g4 + q;
   const bool valid = gi < npts;
-  const int ptot = valid ? info[gi].x : 0;
+  int ptot, ly = 0;
+  if constexpr (LEAN) {  // (p, +-level) as the fill's solve left them
+    const int2 pi = valid ? info[gi] : make_int2(0, 0);
+    ptot = pi.x;
+    ly = pi.x > 0 ? pi.y : 0;
+  } else {
+    ptot = valid ? info[gi].x : 0;
+  }
   const bool pre = l < J0;
 
   // ---- the factor's loads: the wave's four factors through a buffer resource, as
@@ -673,7 +714,8 @@ __device__ __forceinline__ void tq40_factor_hit(const SolveConsts &c, const Slab
   });
   __syncthreads();
 
-  tq40_factor_solve<KP, true, LEAN>(c, slab, sm, A, xv, g0, valid, ptot, gi, q, l, info);
+  tq40_factor_solve<KP, true, LEAN>(c, slab, sm, A, xv, g0, valid, ptot, gi, q, l, info, ly,
+                                    cuts);
 }
 
 }  // namespace cwbl

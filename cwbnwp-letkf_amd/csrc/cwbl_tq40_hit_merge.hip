@@ -16,31 +16,34 @@ namespace cwbl {
 // loading it, where the batches are equal, measured the same as the load.
 // The block is the LEAN form of that text (cwbl_tq40_factor.h): the same expressions on the
 // same bits with fewer VALU instructions around them (profiles/hit_lean.txt); the per-batch
-// kernel and the fill keep the plain form and their register figures.
+// kernel and the fill keep the plain form and their register figures.  info holds what the
+// fill's solves stored, so a solved point's level is read, not derived (cuts: HitLevelCuts,
+// cwbl_internal.h; profiles/hit_masks.txt).
 template <int KP>
 __global__ void __launch_bounds__(64, 2)
 solve_tq40_factor_merged_kernel(SolveConsts c, SlabDev slab, const HitSeg *__restrict__ seg,
                                 const double *__restrict__ ws, const double *__restrict__ aux,
-                                int2 *__restrict__ info) {
+                                int2 *__restrict__ info, HitLevelCuts cuts) {
   const HitSeg sg = seg[blockIdx.y];
   const int nblk = (sg.ns + 3) >> 2;
   if ((int)blockIdx.x >= nblk) return;  // (the whole block: a row is as wide as the largest segment)
   tq40_factor_hit<KP, true>(c, slab, sg.g0, sg.ns,
                             ws + (size_t)sg.ord * FactorRecord<KP>::WORDS,
                             aux + (size_t)sg.ord * FactorAux<KP>::WORDS, info + sg.info,
-                            blockIdx.x, nblk);
+                            blockIdx.x, nblk, cuts);
 }
 
 hipError_t launch_solve_tq40_factor_merged(hipStream_t s, int kp, SolveConsts c, SlabDev slab,
                                            const HitSeg *seg, int nseg, int maxns,
-                                           const double *ws, const double *aux, int2 *info) {
+                                           const double *ws, const double *aux, int2 *info,
+                                           HitLevelCuts cuts) {
   if (nseg <= 0 || maxns <= 0) return hipSuccess;
   if (c.quad_r == nullptr || aux == nullptr || seg == nullptr || kp != kTq4KP || nseg > 65535 ||
       maxns > (1 << 19))
     return hipErrorInvalidValue;
   const dim3 grid((maxns + 3) / 4, nseg);
   hipLaunchKernelGGL((solve_tq40_factor_merged_kernel<kTq4KP>), grid, dim3(64), 0, s, c, slab,
-                     seg, ws, aux, info);
+                     seg, ws, aux, info, cuts);
   return hipGetLastError();
 }
 
