@@ -209,6 +209,12 @@ struct TreeBufs {
   std::thread worker;
   bool worker_started = false, worker_joined = false, tree_ready = false;
   double worker_ms = 0.0;
+  // CWBL_OPT_INDEX_ORDER = 1 (cell_order): a slot is the position in the bins' cell-sorted
+  // order.  order[p]: the obs index at position p (the columns' slot_obs); rank: its inverse;
+  // ind2[i] = rank[ind[i]]: the tree's slots as positions, composed once the tree is up.  The
+  // solve reads its coordinates from bxyz, whose payload is then p.
+  int cell_order = 0;
+  DevBuf order, rank, ind2;
   void join() {
     if (worker.joinable()) worker.join();
     worker_joined = worker_started;
@@ -217,7 +223,7 @@ struct TreeBufs {
     join();
     nodes.release(); rdata.release(); ind.release(); col_bg.release();
     col_omm.release(); col_err.release(); col_ok.release(); bxyz.release(); bstart.release();
-    ncoord.release();
+    ncoord.release(); order.release(); rank.release(); ind2.release();
   }
   ~TreeBufs() { join(); }
 };
@@ -364,6 +370,7 @@ struct State {
   DevBuf wsf;  // CWBL_OPT_COLUMN_FACTOR: the factors of a (sub-)batch's columns, for the call
   DevBuf flags;                                       // binned search: flagged points (+ count)
   int index_mode = 0;                                 // CWBL_OPT_INDEX
+  int index_order = 0;                                // CWBL_OPT_INDEX_ORDER
   DevBuf tdesc_tree;                                  // index mode 1: the tree searches' table
   DevBuf ix_keys[2], ix_vals[2], ix_hist, ix_part;    // device bin build scratch
   PinBuf ix_pin;                                      // its bounds read-back; the flag counts
@@ -693,6 +700,11 @@ cwbl_transfer_info_t TI;  // cwbl_transfer_info: how it moved a host slab's var
 
 // ---- cwbl_prep_info: what the current cwbl_analyze_var spends on its search index -----------
 cwbl_prep_info_t P;
+// ---- cwbl_index_info / cwbl_index_slots: how the current cwbl_analyze_var numbers its columns --
+cwbl_index_info_t IX;
+struct IndexUse { int family, type_id; TreeBufs *tb; };  // tb lives until release_obs
+std::vector<IndexUse> g_index_use;
+bool g_index_called = false;
 struct PrepSpan { int ev; int kind; };  // kind 0: bins (device build), 1: columns
 std::vector<PrepSpan> g_pspans;
 int g_pev_used = 0;
@@ -733,11 +745,13 @@ void prep_collect() {  // after a synchronisation of S.stream
 // dxyz(3,n) is normalised into ncoord and the bounds are reduced and read back (one
 // synchronisation of s).  div_opt: the divisor, 0 = by density.  Fills the grid of `bins`
 // and, unless grid_only, bxyz / bstart; *skeys / *svals (nullable) point at the sorted cell
-// ids and obs indices in the scratch buffers, valid until the next build.
+// ids and obs indices in the scratch buffers, valid until the next build.  by_position: the
+// payload of bxyz[p] is p, not the obs index (CWBL_OPT_INDEX_ORDER = 1).
 int device_bins(hipStream_t s, const float *dxyz, int n, int tdim, float hinv, float vinv,
                 int div_opt, bool have_bounds, IndexBounds &bounds, DevBuf &ncoord,
                 HostBins &bins, int &div_used, bool grid_only, DevBuf *bxyz, DevBuf &bstart,
-                const int **skeys = nullptr, const int **svals = nullptr) {
+                const int **skeys = nullptr, const int **svals = nullptr,
+                bool by_position = false) {
   if (!have_bounds) {
     const int nblk = index_bound_blocks(n);
     const size_t pbytes = (size_t)nblk * kIndexBoundWords * sizeof(float);
@@ -768,7 +782,7 @@ int device_bins(hipStream_t s, const float *dxyz, int n, int tdim, float hinv, f
   HIPCHK(launch_index_sort(s, n, ncell, ncoord.as<float4>(), tdim, g, keys, vals,
                            S.ix_hist.as<int>(), &which));
   HIPCHK(launch_index_finish(s, ncoord.as<float4>(), n, ncell, keys[which], vals[which],
-                             bxyz ? bxyz->as<float4>() : nullptr, bstart.as<int>()));
+                             bxyz ? bxyz->as<float4>() : nullptr, bstart.as<int>(), by_position));
   if (skeys) *skeys = keys[which];
   if (svals) *svals = vals[which];
   return CWBL_OK;
@@ -798,6 +812,17 @@ void start_tree_worker(TreeBufs *tb, const ObsType &ot, bool dim3) {
   });
 }
 
+// Cell order: the uploaded tree's ind as sorted positions, ind2 = rank[ind], on stream s (rank
+// was written on S.stream before anything was queued on the search stream).
+int compose_ind(TreeBufs *tb, hipStream_t s) {
+  const size_t n = tb->host.ind.size();
+  HIPCHK(tb->ind2.ensure(n * sizeof(int) + 4));
+  HIPCHK(launch_index_compose(s, tb->ind.as<int>(), tb->rank.as<int>(), (int)n,
+                              tb->ind2.as<int>()));
+  ++IX.trees_composed;
+  return CWBL_OK;
+}
+
 // Joins a mode-1 tree's worker and uploads the tree on stream s (once).
 int ready_tree(TreeBufs *tb, hipStream_t s) {
   if (tb->tree_ready) return CWBL_OK;
@@ -820,6 +845,8 @@ int ready_tree(TreeBufs *tb, hipStream_t s) {
   if (!h.ind.empty())
     HIPCHK(hipMemcpyAsync(tb->ind.p, h.ind.data(), h.ind.size() * sizeof(int),
                           hipMemcpyHostToDevice, s));
+  if (tb->cell_order)
+    if (int rc = compose_ind(tb, s)) return rc;
   tb->tree_ready = true;
   return CWBL_OK;
 }
@@ -834,13 +861,14 @@ int index_entry(int entry, int tdim, bool dim3, float hinv, float vinv, int max_
   TreeBufs *tb = nullptr;
   for (auto &t : S.tree_cache)
     if (t->mode == 1 && t->entry == entry && t->dim == tdim && t->hinv == hinv &&
-        (!dim3 || t->vinv == vinv))
+        (!dim3 || t->vinv == vinv) && t->cell_order == S.index_order)
       tb = t.get();
   const bool fresh = !tb;
   if (fresh) {
     auto nt = std::make_unique<TreeBufs>();
     nt->mode = 1; nt->entry = entry; nt->dim = tdim; nt->hinv = hinv; nt->vinv = vinv;
     nt->n = n;
+    nt->cell_order = S.index_order;
     tb = nt.get();
     S.tree_cache.push_back(std::move(nt));
   }
@@ -854,10 +882,22 @@ int index_entry(int entry, int tdim, bool dim3, float hinv, float vinv, int max_
       ot.dxyz_ok = true;
     }
     HIPCHK(prep_begin(S.stream, 0));
+    const int *svals = nullptr;
     if (int rc = device_bins(S.stream, ot.dxyz.as<float>(), n, tdim, hinv, vinv, S.bin_div,
                              !fresh, tb->bounds, tb->ncoord, tb->bins, tb->bin_div_used, false,
-                             &tb->bxyz, tb->bstart))
+                             &tb->bxyz, tb->bstart, nullptr, &svals, tb->cell_order != 0))
       return rc;
+    if (tb->cell_order) {
+      // the sorted obs indices leave the scratch buffers: the slot table and its inverse; a
+      // tree that is already up (a changed divisor) gets its ind composed anew
+      const size_t bytes = (size_t)n * sizeof(int);
+      HIPCHK(tb->order.ensure(bytes));
+      HIPCHK(tb->rank.ensure(bytes));
+      HIPCHK(hipMemcpyAsync(tb->order.p, svals, bytes, hipMemcpyDeviceToDevice, S.stream));
+      HIPCHK(launch_index_rank(S.stream, tb->order.as<int>(), n, tb->rank.as<int>()));
+      if (tb->tree_ready)
+        if (int rc = compose_ind(tb, S.stream)) return rc;
+    }
     HIPCHK(prep_end(S.stream));
     tb->bin_div_opt = S.bin_div;
     ++P.bins_built;
@@ -964,18 +1004,24 @@ int build_family(int family, const cwbl_var_params *vp, std::vector<TreeDesc> &d
     } else {
       is_assim[0] = tp->hclr > 0.0f ? 1 : 0;
     }
-    // (index mode 1: a slot is the obs index, the columns stay in obs order)
+    // (index mode 1: a slot is the obs index, the columns stay in obs order; in cell order
+    // they are gathered through `order`, as mode 0 gathers them through the tree's ind)
+    const int *slot_obs = tb->mode == 0    ? tb->ind.as<int>()
+                          : tb->cell_order ? tb->order.as<int>()
+                                           : nullptr;
     HIPCHK(prep_begin(S.stream, 1));
     HIPCHK(launch_obs_prep(S.stream, S.k, S.kp, family, ot.type_id, ot.nvar, n,
                            ot.obs.as<float>(), ot.error.as<float>(), ot.hdxb.as<float>(),
                            ot.qc.as<int>(), tp->err_muti, tp->err_rej, is_assim, S.norain,
-                           tb->mode == 1 ? nullptr : tb->ind.as<int>(), tb->col_bg.as<float>(),
+                           slot_obs, tb->col_bg.as<float>(),
                            tb->col_omm.as<float>(), tb->col_err.as<float>(),
                            tb->col_ok.as<uint8_t>()));
     HIPCHK(prep_end(S.stream));
     TreeDesc d{};
     if (tb->mode == 1) {  // the solve's table: coordinates by obs index, no tree
-      d.rdata = tb->ncoord.as<float4>();
+      // (cell order: the bins' own points are the coordinates by slot; the solve reads x, y
+      // and z of an rdata entry and never its fourth component, which here holds the slot)
+      d.rdata = tb->cell_order ? tb->bxyz.as<float4>() : tb->ncoord.as<float4>();
     } else {
       d.nodes = tb->nodes.as<TreeNode>();
       d.rdata = tb->rdata.as<float4>();
@@ -1001,11 +1047,13 @@ int build_family(int family, const cwbl_var_params *vp, std::vector<TreeDesc> &d
     if (tb->mode == 0) max_depth = std::max(max_depth, tb->depth);
     descs.push_back(d);
     tbs.push_back(tb);
+    g_index_use.push_back({family, ot.type_id, tb});
   }
   return CWBL_OK;
 }
 
 void release_obs() {
+  g_index_use.clear();
   for (auto &t : S.tree_cache) t->release();
   S.tree_cache.clear();
   for (auto &o : S.obs) {
@@ -1329,7 +1377,7 @@ int ready_trees(VarCall &v, hipStream_t s) {
     if (int rc = ready_tree(tb, s)) return rc;
     sd[i].nodes = tb->nodes.as<TreeNode>();
     sd[i].rdata = tb->rdata.as<float4>();
-    sd[i].ind = tb->ind.as<int>();
+    sd[i].ind = tb->cell_order ? tb->ind2.as<int>() : tb->ind.as<int>();
     v.max_depth = std::max(v.max_depth, tb->depth);
   }
   HIPCHK(S.tdesc_tree.ensure(sd.size() * sizeof(TreeDesc)));
@@ -1346,6 +1394,11 @@ int plan_trees(VarCall &v) {
   if (int rc = build_family(0, v.vp, v.descs, v.list_cap, v.max_depth, v.tbs)) return rc;
   if (int rc = build_family(1, v.vp, v.descs, v.list_cap, v.max_depth, v.tbs)) return rc;
   v.nt = (int)v.descs.size();
+  IX.index_mode = S.index_mode;
+  IX.types = v.nt;
+  IX.cell_order = v.nt > 0 ? 1 : 0;
+  for (const TreeBufs *tb : v.tbs)
+    if (!tb->cell_order) IX.cell_order = 0;
   if (v.nt == 0 || v.npts == 0) return CWBL_OK;
   HIPCHK(S.tdesc.ensure(v.descs.size() * sizeof(TreeDesc)));
   HIPCHK(hipMemcpyAsync(S.tdesc.p, v.descs.data(), v.descs.size() * sizeof(TreeDesc),
@@ -2340,6 +2393,7 @@ int cwbl_init(const cwbl_init_params *p) {
   S.pageable_register = true;
   S.bin_div = 0;  // 0: by density (bin_div_for)
   S.index_mode = 0;
+  S.index_order = 0;
   S.column_share = 0;
   S.column_levels = 0;
   S.column_factor = false;
@@ -2353,6 +2407,9 @@ int cwbl_init(const cwbl_init_params *p) {
   S.host_pipe = false;
   S.ncu = prop.multiProcessorCount;
   std::memset(&P, 0, sizeof P);
+  std::memset(&IX, 0, sizeof IX);
+  g_index_use.clear();
+  g_index_called = false;
   std::memset(&CI, 0, sizeof CI);
   std::memset(&CR, 0, sizeof CR);
   std::memset(&TI, 0, sizeof TI);
@@ -2454,6 +2511,10 @@ int cwbl_set_option(int option, long long value) {
     case CWBL_OPT_INDEX:
       if (!range(0, 1)) break;
       S.index_mode = (int)value;
+      return CWBL_OK;
+    case CWBL_OPT_INDEX_ORDER:
+      if (!range(0, 1)) break;
+      S.index_order = (int)value;  // (read under CWBL_OPT_INDEX = 1 only: index_entry)
       return CWBL_OK;
     case CWBL_OPT_COLUMN_SHARE:
       if (!range(0, 2)) break;
@@ -2664,6 +2725,9 @@ static int begin_call(const cwbl_slab *sl) {
   S.kev_used = 0;
   g_bounce_ms = 0.0;
   std::memset(&P, 0, sizeof P);
+  std::memset(&IX, 0, sizeof IX);
+  g_index_use.clear();
+  g_index_called = true;
   std::memset(&R, 0, sizeof R);
   std::memset(&CI, 0, sizeof CI);
   std::memset(&CR, 0, sizeof CR);
@@ -3439,6 +3503,38 @@ int cwbl_prep_info(cwbl_prep_info_t *out) {
   if (int rc = require_device()) return rc;
   if (!out) return fail(CWBL_ERR_ARG, "cwbl_prep_info: null argument");
   *out = P;
+  return CWBL_OK;
+}
+
+int cwbl_index_info(cwbl_index_info_t *out) {
+  if (int rc = require_device()) return rc;
+  if (!out) return fail(CWBL_ERR_ARG, "cwbl_index_info: null argument");
+  *out = IX;
+  return CWBL_OK;
+}
+
+int cwbl_index_slots(int family, int type_id, int cap, int *slot_obs, int *n) {
+  if (int rc = require_device()) return rc;
+  if (!n || cap < 0 || (cap > 0 && !slot_obs))
+    return fail(CWBL_ERR_ARG, "cwbl_index_slots: bad arguments");
+  if (!g_index_called) return fail(CWBL_ERR_STATE, "cwbl_index_slots before cwbl_analyze_var");
+  const TreeBufs *tb = nullptr;
+  for (const IndexUse &u : g_index_use)
+    if (u.family == family && u.type_id == type_id) tb = u.tb;
+  if (!tb)
+    return fail(CWBL_ERR_ARG, "cwbl_index_slots: the last call used no obs type %d of family %d",
+                type_id, family);
+  *n = tb->n;
+  const int m = std::min(cap, tb->n);
+  if (m <= 0) return CWBL_OK;
+  if (tb->mode == 1 && !tb->cell_order) {  // a slot is the obs index
+    for (int i = 0; i < m; ++i) slot_obs[i] = i;
+    return CWBL_OK;
+  }
+  const DevBuf &src = tb->mode == 0 ? tb->ind : tb->order;
+  HIPCHK(hipMemcpyAsync(slot_obs, src.p, (size_t)m * sizeof(int), hipMemcpyDeviceToHost,
+                        S.stream));
+  HIPCHK(hipStreamSynchronize(S.stream));
   return CWBL_OK;
 }
 

@@ -13,6 +13,12 @@
 //   index_starts_kernel         bstart[c] = first sorted position with cell id >= c
 //   index_fill_kernel           bxyz[p] = (x, y, z, obs index as int bits) + the kBinPad tail
 //
+// and, for columns numbered in the bins' cell order (CWBL_OPT_INDEX_ORDER = 1):
+//
+//   index_fill_pos_kernel       index_fill_kernel with the sorted position p itself as payload
+//   index_rank_kernel           rank[order[p]] = p: the inverse of the sorted obs indices
+//   index_compose_kernel        ind2[i] = rank[ind[i]]: a k-d tree's slots as sorted positions
+//
 // Nothing here depends on the order in which blocks or atomics complete: integer atomics only
 // count (the LDS digit histograms), positions come from scans and in-wave ranks.
 #include "cwbl_internal.h"
@@ -238,6 +244,41 @@ index_fill_kernel(const float4 *__restrict__ ncoord, const int *__restrict__ sva
   bxyz[p] = o;
 }
 
+// index_fill_kernel for slots in cell order: point p carries its own position
+__global__ void __launch_bounds__(256)
+index_fill_pos_kernel(const float4 *__restrict__ ncoord, const int *__restrict__ svals, int n,
+                      float4 *__restrict__ bxyz) {
+  const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= (long long)n + kBinPad) return;
+  float4 o = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  if (p < n) {
+    const int i = svals[p];
+    if ((unsigned)i < (unsigned)n) {  // always: svals is a permutation of 0..n-1
+      o = ncoord[i];
+      o.w = __int_as_float((int)p);
+    }
+  }
+  bxyz[p] = o;
+}
+
+// order is a permutation of 0..n-1: every rank[] entry is written once, by one thread
+__global__ void __launch_bounds__(256)
+index_rank_kernel(const int *__restrict__ order, int n, int *__restrict__ rank) {
+  const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= n) return;
+  const int i = order[p];
+  if ((unsigned)i < (unsigned)n) rank[i] = (int)p;
+}
+
+__global__ void __launch_bounds__(256)
+index_compose_kernel(const int *__restrict__ ind, const int *__restrict__ rank, int n,
+                     int *__restrict__ ind2) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int o = ind[i];
+  ind2[i] = (unsigned)o < (unsigned)n ? rank[o] : 0;  // always: ind is a permutation of 0..n-1
+}
+
 }  // namespace
 
 int index_bound_blocks(int n) {
@@ -298,12 +339,30 @@ hipError_t launch_index_sort(hipStream_t s, int n, int ncell, const float4 *ncoo
 }
 
 hipError_t launch_index_finish(hipStream_t s, const float4 *ncoord, int n, int ncell,
-                               const int *skeys, const int *svals, float4 *bxyz, int *bstart) {
+                               const int *skeys, const int *svals, float4 *bxyz, int *bstart,
+                               bool by_position) {
   hipLaunchKernelGGL(index_starts_kernel, dim3((unsigned)((ncell + 1 + 255) / 256)), dim3(256), 0,
                      s, skeys, n, ncell, bstart);
-  if (bxyz)
+  if (bxyz && by_position)
+    hipLaunchKernelGGL(index_fill_pos_kernel, dim3((unsigned)((n + kBinPad + 255) / 256)),
+                       dim3(256), 0, s, ncoord, svals, n, bxyz);
+  else if (bxyz)
     hipLaunchKernelGGL(index_fill_kernel, dim3((unsigned)((n + kBinPad + 255) / 256)), dim3(256),
                        0, s, ncoord, svals, n, bxyz);
+  return hipGetLastError();
+}
+
+hipError_t launch_index_rank(hipStream_t s, const int *order, int n, int *rank) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(index_rank_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, order,
+                     n, rank);
+  return hipGetLastError();
+}
+
+hipError_t launch_index_compose(hipStream_t s, const int *ind, const int *rank, int n, int *ind2) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(index_compose_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
+                     ind, rank, n, ind2);
   return hipGetLastError();
 }
 

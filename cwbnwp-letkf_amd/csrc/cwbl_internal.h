@@ -43,7 +43,10 @@ struct TreeDesc {
   // column table of this type for the current variable, one column per (tree slot,
   // obs-var): column slot*nvar + v belongs to obs ind[slot].  With the device-built index
   // (CWBL_OPT_INDEX = 1) a slot is the obs index itself: the solve's table then has rdata in
-  // obs order, and the tree searches get a second table with the tree's own rdata.
+  // obs order, and the tree searches get a second table with the tree's own rdata.  Under
+  // CWBL_OPT_INDEX_ORDER = 1 a slot is the position in the bins' cell-sorted order: the solve's
+  // rdata is bxyz itself (no reader of the solve's table uses an entry's fourth component), and
+  // the tree searches' ind is the tree's permutation composed with the positions.
   const float    *col_bg;     // [n*nvar][KP] fp32 bg = hdxb - mean, zero padded
   const float    *col_omm;    // [n*nvar] obs - mean
   const float    *col_err;    // [n*nvar] error * err_muti
@@ -102,9 +105,14 @@ void index_finish_bounds(const float *part, int nblocks, IndexBounds &b);  // ho
 hipError_t launch_index_sort(hipStream_t s, int n, int ncell, const float4 *ncoord, int dim,
                              IndexGrid g, int *keys[2], int *vals[2], int *hist, int *which);
 // bstart[0..ncell] from the sorted cell ids and (bxyz non-null) the bin payload of n + kBinPad
-// points
+// points: the obs index, or (by_position) the sorted position itself
 hipError_t launch_index_finish(hipStream_t s, const float4 *ncoord, int n, int ncell,
-                               const int *skeys, const int *svals, float4 *bxyz, int *bstart);
+                               const int *skeys, const int *svals, float4 *bxyz, int *bstart,
+                               bool by_position = false);
+// CWBL_OPT_INDEX_ORDER = 1: rank[order[p]] = p for the sorted obs indices order[0..n), and a
+// tree's ind as sorted positions, ind2[i] = rank[ind[i]]
+hipError_t launch_index_rank(hipStream_t s, const int *order, int n, int *rank);
+hipError_t launch_index_compose(hipStream_t s, const int *ind, const int *rank, int n, int *ind2);
 
 // Per-variable constants of the solve.
 struct SolveConsts {

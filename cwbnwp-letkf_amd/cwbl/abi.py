@@ -32,6 +32,7 @@ OPT_INFO_WINDOW, OPT_INDEX, OPT_RECORD_REUSE = 12, 13, 14
 OPT_COLUMN_SHARE, OPT_COLUMN_LEVELS, OPT_FACTOR_REUSE, OPT_HIT_MERGE = 15, 16, 17, 18
 OPT_WAVE_REUSE, OPT_HOST_PIPE, OPT_BIG_REUSE, OPT_ROWS_REUSE = 19, 20, 21, 22
 OPT_COLUMN_FACTOR, OPT_COLUMN_REUSE, OPT_COLUMN_ROWS = 23, 24, 25
+OPT_INDEX_ORDER = 26
 OPTIONS = {"solver": OPT_SOLVER, "split40": OPT_SPLIT40, "split40_batch": OPT_SPLIT40_BATCH,
            "search": OPT_SEARCH,
            "big_path": OPT_BIG_PATH, "big_batch": OPT_BIG_BATCH, "pageable": OPT_PAGEABLE,
@@ -42,7 +43,8 @@ OPTIONS = {"solver": OPT_SOLVER, "split40": OPT_SPLIT40, "split40_batch": OPT_SP
            "hit_merge": OPT_HIT_MERGE, "wave_reuse": OPT_WAVE_REUSE,
            "host_pipe": OPT_HOST_PIPE, "big_reuse": OPT_BIG_REUSE,
            "rows_reuse": OPT_ROWS_REUSE, "column_factor": OPT_COLUMN_FACTOR,
-           "column_reuse": OPT_COLUMN_REUSE, "column_rows": OPT_COLUMN_ROWS}
+           "column_reuse": OPT_COLUMN_REUSE, "column_rows": OPT_COLUMN_ROWS,
+           "index_order": OPT_INDEX_ORDER}
 
 #: cwbl_column_info_t.reason
 (COLUMN_SHARED, COLUMN_REASON_OFF, COLUMN_REASON_3D, COLUMN_REASON_Q1, COLUMN_REASON_NZ,
@@ -132,6 +134,14 @@ class PrepInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class IndexInfo(C.Structure):
+    _fields_ = [("index_mode", C.c_int), ("cell_order", C.c_int), ("types", C.c_int),
+                ("trees_composed", C.c_int)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class ReuseInfo(C.Structure):
     _fields_ = [("batches_reused", C.c_longlong), ("batches_assembled", C.c_longlong),
                 ("bytes_held", C.c_longlong), ("ms_compare", C.c_double)]
@@ -174,7 +184,8 @@ EXPORTS = ["cwbl_init", "cwbl_set_stream", "cwbl_set_obs", "cwbl_analyze_var", "
            "cwbl_solve_batch", "cwbl_search",
            "cwbl_pack_columns", "cwbl_unpack_columns", "cwbl_pack_members",
            "cwbl_unpack_members", "cwbl_vcoord_mean", "cwbl_member_sum", "cwbl_scale", "cwbl_set_kernel_timing", "cwbl_kernel_times",
-           "cwbl_set_option", "cwbl_bin_index", "cwbl_prep_info", "cwbl_reuse_info",
+           "cwbl_set_option", "cwbl_bin_index", "cwbl_prep_info", "cwbl_index_info",
+           "cwbl_index_slots", "cwbl_reuse_info",
            "cwbl_column_info", "cwbl_column_reuse_info", "cwbl_transfer_info", "cwbl_finalize",
            "cwbl_last_error", "cwbl_abi_version"]
 
@@ -368,6 +379,12 @@ def load_library(path=None):
     if hasattr(lib, "cwbl_column_reuse_info"):
         lib.cwbl_column_reuse_info.argtypes = [C.POINTER(ColumnReuseInfo)]
         lib.cwbl_column_reuse_info.restype = C.c_int
+    # (nor has a library from before the cell-order numbering its two entry points)
+    if hasattr(lib, "cwbl_index_info"):
+        lib.cwbl_index_info.argtypes = [C.POINTER(IndexInfo)]
+        lib.cwbl_index_info.restype = C.c_int
+        lib.cwbl_index_slots.argtypes = [C.c_int, C.c_int, C.c_int, vp, C.POINTER(C.c_int)]
+        lib.cwbl_index_slots.restype = C.c_int
     lib.cwbl_finalize.argtypes = []
     lib.cwbl_last_error.restype = cp
     lib.cwbl_abi_version.restype = C.c_int
@@ -503,6 +520,27 @@ class Core:
         info = PrepInfo()
         self._check(self.lib.cwbl_prep_info(C.byref(info)))
         return info
+
+    def index_info(self):
+        """cwbl_index_info: how the last analyze_var numbered its obs types' columns
+        (IndexInfo; the "index" and "index_order" options)."""
+        if not hasattr(self.lib, "cwbl_index_info"):
+            raise CwblError("the loaded library has no cwbl_index_info")
+        info = IndexInfo()
+        self._check(self.lib.cwbl_index_info(C.byref(info)))
+        return info
+
+    def index_slots(self, family, type_id):
+        """cwbl_index_slots: the slot -> obs index table (int32, 0-based) the last analyze_var
+        used for obs type `type_id` of `family` (0 GTS, 1 radar)."""
+        if not hasattr(self.lib, "cwbl_index_slots"):
+            raise CwblError("the loaded library has no cwbl_index_slots")
+        n = C.c_int(0)
+        self._check(self.lib.cwbl_index_slots(int(family), int(type_id), 0, None, C.byref(n)))
+        slots = np.empty(n.value, np.int32)
+        self._check(self.lib.cwbl_index_slots(int(family), int(type_id), n.value, _ptr(slots),
+                                              C.byref(n)))
+        return slots
 
     def reuse_info(self):
         """cwbl_reuse_info: what the last analyze_var solved from kept records (ReuseInfo)."""

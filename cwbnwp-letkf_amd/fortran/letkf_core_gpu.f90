@@ -103,6 +103,9 @@ module letkf_core_gpu
     ! CWBL_OPT_COLUMN_FACTOR and CWBL_OPT_COLUMN_REUSE, as KP = 96 is (0, default: they are
     ! ignored there and a shared call runs the level chunks)
     integer(c_int), parameter, public :: CWBL_OPT_COLUMN_ROWS = 25
+    ! cwbl_set_option: under CWBL_OPT_INDEX = 1 a column's slot is its position in the cell-sorted
+    ! order of its type's bins (1; 0, default: its obs index); bit-identical results
+    integer(c_int), parameter, public :: CWBL_OPT_INDEX_ORDER = 26
     ! cwbl_column_reuse_info_t%form
     integer(c_int), parameter, public :: CWBL_COLUMN_FORM_NONE = 0
     integer(c_int), parameter, public :: CWBL_COLUMN_FORM_RECORDS = 1
@@ -127,6 +130,10 @@ module letkf_core_gpu
         integer(c_int) :: trees_built, bins_built, bins_on_device, flagged_batches
         real(c_double) :: ms_tree, ms_bins, ms_columns, ms_tree_wait
     end type cwbl_prep_info_t
+
+    type, bind(C), public :: cwbl_index_info_t     ! cwbl_index_info
+        integer(c_int) :: index_mode, cell_order, types, trees_composed
+    end type cwbl_index_info_t
 
     type, bind(C), public :: cwbl_reuse_info_t     ! cwbl_reuse_info
         integer(c_long_long) :: batches_reused, batches_assembled, bytes_held
@@ -164,7 +171,8 @@ module letkf_core_gpu
               cwbl_pack_columns, cwbl_unpack_columns, cwbl_pack_members, cwbl_unpack_members, &
               cwbl_vcoord_mean, &
               cwbl_member_sum, cwbl_scale, cwbl_set_stream, cwbl_set_option, &
-              cwbl_bin_index, cwbl_prep_info, cwbl_reuse_info, cwbl_column_info, &
+              cwbl_bin_index, cwbl_prep_info, cwbl_index_info, cwbl_index_slots, &
+              cwbl_reuse_info, cwbl_column_info, &
               cwbl_column_reuse_info, cwbl_transfer_info, &
               cwbl_finalize, cwbl_abi_version, cwbl_error, cwbl_check
     ! host obs ingest (include/cwb_letkf_ingest.h); file names and varname are passed as
@@ -375,6 +383,21 @@ module letkf_core_gpu
             import :: c_int, cwbl_prep_info_t
             type(cwbl_prep_info_t), intent(out) :: info
         end function cwbl_prep_info
+
+        ! how the last cwbl_analyze_var numbered its obs types' columns (CWBL_OPT_INDEX_ORDER)
+        integer(c_int) function cwbl_index_info(info) bind(C, name='cwbl_index_info')
+            import :: c_int, cwbl_index_info_t
+            type(cwbl_index_info_t), intent(out) :: info
+        end function cwbl_index_info
+
+        ! the slot -> obs index table (0-based) it used for one obs type, into host memory
+        integer(c_int) function cwbl_index_slots(family, type_id, cap, slot_obs, n) &
+                bind(C, name='cwbl_index_slots')
+            import :: c_int, c_ptr
+            integer(c_int), value       :: family, type_id, cap
+            type(c_ptr),    value       :: slot_obs
+            integer(c_int), intent(out) :: n
+        end function cwbl_index_slots
 
         ! what the last cwbl_analyze_var solved from kept records (CWBL_OPT_RECORD_REUSE)
         integer(c_int) function cwbl_reuse_info(info) bind(C, name='cwbl_reuse_info')

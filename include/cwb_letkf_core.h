@@ -534,7 +534,7 @@ enum {
                                 * path at KP = 128 is served as well, as at KP = 96: the kept
                                 * factor is the BigFactor<128, 64> (8705 words, 69.6 KB per column)
                                 * and a hit runs solve_tqb_factor_column_all_kernel<128, 64> */
-  CWBL_OPT_COLUMN_ROWS = 25    /* 1: the hand-off path at KP = 128 (the ensemble sizes above 96
+  CWBL_OPT_COLUMN_ROWS = 25,   /* 1: the hand-off path at KP = 128 (the ensemble sizes above 96
                                 * up to 128, default solver, CWBL_OPT_BIG_PATH = 1) becomes
                                 * eligible for CWBL_OPT_COLUMN_FACTOR and CWBL_OPT_COLUMN_REUSE,
                                 * which then hold there as they hold at KP = 96: the fill of
@@ -556,6 +556,25 @@ enum {
                                 * Accepted and ignored at the ensemble sizes up to 96, under
                                 * CWBL_OPT_BIG_PATH = 0, under CWBL_OPT_SOLVER = 1 and for group
                                 * calls.  Setting it starts a new generation of both caches */
+  CWBL_OPT_INDEX_ORDER = 26    /* how CWBL_OPT_INDEX = 1 numbers an obs type's columns.  0
+                                * (default; cwbl_init resets it): a column's slot is its obs
+                                * index, and every call launches what it launches without the
+                                * option.  1: the slot is the position in the cell-sorted order of
+                                * the type's bins (cwbl_bin_index's `order`), so the columns of one
+                                * neighbourhood lie close together, as they do in the k-d tree's
+                                * slot order of CWBL_OPT_INDEX = 0.  Per type the library then
+                                * keeps the sorted obs indices and their inverse (4 bytes per obs
+                                * each) and, for a type whose tree is walked, the tree's slots as
+                                * positions (4 bytes per obs); the solve reads its coordinates
+                                * from the bins' own points, the columns are gathered through the
+                                * sorted obs indices.  The neighbour lists keep their order (the
+                                * cells visited, ascending obs index within a cell, kdtree2's
+                                * order where a list truncates): only the labels change, so
+                                * results are bit-identical to 0 with equal counters.  A changed
+                                * CWBL_OPT_BIN_DIV rebuilds the bins and the numbering and keeps
+                                * the tree.  Accepted and ignored under CWBL_OPT_INDEX = 0.
+                                * Setting it starts a new generation of both caches; see
+                                * cwbl_index_info and cwbl_index_slots */
 };
 int         cwbl_set_option(int option, long long value);
 
@@ -594,6 +613,25 @@ typedef struct cwbl_prep_info_t {
   double ms_tree_wait;     /* CWBL_OPT_INDEX = 1: time the call waited for a tree worker */
 } cwbl_prep_info_t;
 int         cwbl_prep_info(cwbl_prep_info_t *out);
+
+/* How the last cwbl_analyze_var numbered the columns of its obs types (a call served entirely
+ * from the record or column cache plans no index and reports types = 0). */
+typedef struct cwbl_index_info_t {
+  int index_mode;      /* CWBL_OPT_INDEX of the call */
+  int cell_order;      /* 1: every obs type of the call was numbered in the cell order of its
+                        * bins (CWBL_OPT_INDEX = 1 with CWBL_OPT_INDEX_ORDER = 1) */
+  int types;           /* obs types the call searched */
+  int trees_composed;  /* k-d trees whose slots the call rewrote as cell-order positions: a tree
+                        * first needed by a search, or one already up when the bins changed */
+} cwbl_index_info_t;
+int         cwbl_index_info(cwbl_index_info_t *out);
+/* The slot -> obs index (0-based) table the last cwbl_analyze_var used for one obs type
+ * (family 0 GTS, 1 radar; type_id as in cwbl_obs_set), copied to host memory: the k-d tree's
+ * permutation under CWBL_OPT_INDEX = 0, the identity under CWBL_OPT_INDEX = 1, and
+ * cwbl_bin_index's `order` under CWBL_OPT_INDEX = 1 with CWBL_OPT_INDEX_ORDER = 1.  *n is the
+ * type's obs count; min(cap, *n) entries of slot_obs are written.  CWBL_ERR_STATE before the
+ * first cwbl_analyze_var, CWBL_ERR_ARG for a type the call did not use. */
+int         cwbl_index_slots(int family, int type_id, int cap, int *slot_obs, int *n);
 
 /* What the last cwbl_analyze_var reused (CWBL_OPT_RECORD_REUSE). */
 typedef struct cwbl_reuse_info_t {

@@ -1,5 +1,7 @@
 #!/usr/bin/env python
-"""Cold and warm cwbl_analyze_var per search-index mode (CWBL_OPT_INDEX) at full-size C2 and C5.
+"""Cold and warm cwbl_analyze_var per search-index mode (CWBL_OPT_INDEX, and mode 1 with the
+columns numbered in the bins' cell order, CWBL_OPT_INDEX_ORDER = 1: the lines "1+o") at full-size
+C2 and C5.
 
 cold: a fresh cwbl_set_obs (which drops every cached index) plus the first cwbl_analyze_var,
       which builds the index: mode 0 the k-d tree and the bins on the host, mode 1 the bins on
@@ -24,7 +26,11 @@ sys.path.insert(0, os.path.join(REPO, "cwbnwp-letkf_amd"))
 from cwbl import abi, synth  # noqa: E402
 
 
-def measure(w, mode, reps, warm):
+#: (label, options) per measured mode, in the order of the table
+MODES = ((0, {"index": 0}), (1, {"index": 1}), ("1+o", {"index": 1, "index_order": 1}))
+
+
+def measure(w, options, reps, warm):
     import torch
     dev = torch.device("cuda:0")
     to_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
@@ -33,7 +39,7 @@ def measure(w, mode, reps, warm):
     var0 = to_dev(w.var)
     var = var0.clone()
     torch.cuda.synchronize()
-    core = abi.Core(w.k, device=0, options={"index": mode})
+    core = abi.Core(w.k, device=0, options=options)
     slab = abi.make_slab(x, y, alt, var, memory=abi.MEM_DEVICE)
 
     def obs_set():
@@ -88,12 +94,12 @@ def main():
         print("mode  set_obs ms  first ms   cold ms   warm ms  cold/warm  first/warm   "
               "ms_prep cold / warm")
         best = {}
-        for mode in (0, 1):
-            rows, kt = measure(w, mode, args.reps, args.warm)
+        for mode, options in MODES:
+            rows, kt = measure(w, options, args.reps, args.warm)
             for r in rows:
                 wm = float(np.median(r["warm"]))
                 cold = r["ms_set"] + r["ms_first"]
-                print(f"{mode:4d}  {r['ms_set']:10.2f} {r['ms_first']:9.2f} {cold:9.2f} {wm:9.2f} "
+                print(f"{mode:>4}  {r['ms_set']:10.2f} {r['ms_first']:9.2f} {cold:9.2f} {wm:9.2f} "
                       f"{cold / wm:10.3f} {r['ms_first'] / wm:11.3f}   {r['ms_prep']:8.2f} / "
                       f"{r['ms_prep_warm']:.2f}", flush=True)
             r = min(rows, key=lambda q: q["ms_first"])
@@ -111,11 +117,14 @@ def main():
                   f"{r['ms_solve']:.2f} ms; per kernel (event-timed call): "
                   + ", ".join(f"{n.split('<')[0]} {v['ms']:.2f}" for n, v in kt.items()), flush=True)
         for key in ("solved", "nobs_sum", "lz_truncated"):
-            assert best[0][key] == best[1][key], (key, best[0][key], best[1][key])
-        f0, f1 = best[0]["ms_first"], best[1]["ms_first"]
-        w0, w1 = (float(np.median(best[m]["warm"])) for m in (0, 1))
+            assert best[0][key] == best[1][key] == best["1+o"][key], (key, best)
+        f0, f1, fo = (best[m]["ms_first"] for m, _ in MODES)
+        w0, w1, wo = (float(np.median(best[m]["warm"])) for m, _ in MODES)
         print(f"   first call, mode 1 against mode 0: {f1:.2f} / {f0:.2f} ms = {f1 / f0:.3f}; "
-              f"warm: {w1:.2f} / {w0:.2f} ms = {w1 / w0:.3f}\n", flush=True)
+              f"warm: {w1:.2f} / {w0:.2f} ms = {w1 / w0:.3f}", flush=True)
+        print(f"   first call, mode 1 in cell order against mode 0: {fo:.2f} / {f0:.2f} ms = "
+              f"{fo / f0:.3f}; warm: {wo:.2f} / {w0:.2f} ms = {wo / w0:.3f} "
+              f"(against mode 1: {wo / w1:.3f})\n", flush=True)
 
 
 if __name__ == "__main__":
